@@ -23,6 +23,11 @@ BASELINE.json metric.  Workloads (frames synthetic, include/sg_synth.h, generate
                    files (host-pull path: reads + PCIe + kernels), the CPU reference configuration.
 
 One step = one pass of the workload.  Rank 0 prints ONE JSON line (fields: README / DESIGN.md).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes
+runs of its own: the CPU baseline (the oracle on a sample of the workload), sum-fits' check of
+the result against the oracle, and at N GPUs the configs[3] strong form timed after the weak one.
+--dump-outputs DIR (1 GPU) writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -54,7 +59,13 @@ def parse():
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=4096)
     ap.add_argument("--rejection", default="sigma")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, sum-fits' oracle "
+                         "check, and at N GPUs (weak form) the configs[3] strong form timed after it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1 GPU: after the timed steps write the last step's results (the stacked image or a "
+                         "fixed seeded sample of it, rejection counters, registration shifts) as DIR/<name>.npy")
     ap.add_argument("--normalize", choices=["none", "additive", "additive-scaling", "multiplicative-scaling"], default="none",
                     help="sigma workload: per-frame normalisation (synthetic location / scale, as "
                          "compute_normalization derives them)")
@@ -84,7 +95,38 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="OpenMP threads of the CPU baseline (default: the CPUs this process may run on, "
                          "sched_getaffinity, capped by the cgroup's cpu.max quota)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs writes one GPU's results: use it with --gpus 1")
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    return args
+
+
+DUMP_SAMPLE = 8 << 20      # elements of an image kept by --dump-outputs (32 MiB as float32)
+
+
+def dump_outputs(path, image, **small):
+    """--dump-outputs: `image` (u16, any shape) as float32 `stack.npy`, whole when it has at most
+    DUMP_SAMPLE elements, else the elements at a fixed seeded choice of DUMP_SAMPLE flat indices in
+    ascending order (the same indices in every run and every build); `small` arrays as float64"""
+    import numpy as np
+    flat = np.ascontiguousarray(image).reshape(-1)
+    if flat.size > DUMP_SAMPLE:
+        idx = np.random.default_rng(0x5151).choice(flat.size, size=DUMP_SAMPLE, replace=False)
+        idx.sort()
+        flat = flat[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "stack.npy"), flat.astype(np.float32))
+    for name, a in small.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def device_u16(t):
+    """a device int16 tensor holding u16 samples, as a host uint16 array"""
+    import numpy as np
+    return t.cpu().numpy().view(np.uint16)
 
 
 def cpu_share():
@@ -493,11 +535,15 @@ def sigma_form(args, ctx, D, strong, gather_mode):
         rej_tot = sd.sum_counters(rej_tot, D.dist, device=D.cdev)   # rejection counters, :1796-1817
     del frames
     torch.cuda.synchronize()
+    out_band = None
+    if args.dump_outputs:       # rows [b, e) as the last timed step's call wrote them
+        last = pipe.bufs[(pipe.k - 1) % pipe.nslots] if gathering and gather_mode == "overlap" else band_out
+        out_band = device_u16(last).reshape(hband, W)[:e - b]
     torch.cuda.set_stream(prev_stream)
     torch.cuda.empty_cache()
     return {"elapsed": elapsed, "kavg": kavg, "per_rank_kms": per_rank_kms, "rej_tot": rej_tot, "st": st,
             "b": b, "e": e, "N": N, "H": H, "W": W, "Htot": Htot, "hband": hband, "nb": nb, "strong": strong,
-            "median": median, "sig": sig, "gather": gather_mode if gathering else "none"}
+            "median": median, "sig": sig, "gather": gather_mode if gathering else "none", "out": out_band}
 
 
 def main_sigma(args):
@@ -511,9 +557,9 @@ def main_sigma(args):
     strong = args.scaling == "strong" or world == 1
     gmode = args.strong_gather if (world > 1 or args.band_of > 1) else "none"
     f = sigma_form(args, ctx, D, strong, gmode)
-    # at N > 1 in the (default) weak form, configs[3]'s strong form is timed after it and reported
-    # beside it: the one 512-frame 4096-row sequence in N row bands, gathered to rank 0
-    f_strong = sigma_form(args, ctx, D, True, args.strong_gather) if world > 1 and not strong else None
+    # --full at N > 1 in the (default) weak form: configs[3]'s strong form is timed after it and
+    # reported beside it, the one 512-frame 4096-row sequence in N row bands, gathered to rank 0
+    f_strong = sigma_form(args, ctx, D, True, args.strong_gather) if args.full and world > 1 and not strong else None
     N, H, W, b, e = f["N"], f["H"], f["W"], f["b"], f["e"]
     elapsed, kavg, st, median = f["elapsed"], f["kavg"], f["st"], f["median"]
     ms_step = elapsed / args.steps * 1e3
@@ -579,7 +625,9 @@ def main_sigma(args):
                 "ms_per_step": round(fs["elapsed"] / args.steps * 1e3, 3), "scaling": "strong",
                 "per_rank_kernel_ms": [round(x, 3) for x in fs["per_rank_kms"]],
                 "rejected": [int(x) for x in np.asarray(fs["rej_tot"]).reshape(-1)[:2]]}
-        if not args.no_cpu_baseline and world == 1 and nb == 1:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, f["out"], rejected=f["rej_tot"])
+        if args.cpu_baseline and world == 1 and nb == 1:
             res["cpu_baseline"] = cpu_baseline(args, N, W, median)
         print(json.dumps(res), flush=True)
     ctx.close()
@@ -698,7 +746,7 @@ def main_config(args):
             stage_keep.append(keep)
             t3 = time.perf_counter()
             stage[:] += (t1 - t0, t2 - t1, t3 - t2)
-            out["sx"], out["sy"] = sx, sy
+            out["sx"], out["sy"], out["q"] = sx, sy, q
             return
         desc, keep = sg.make_desc(sg.MEAN, N, W, H, C, rejection=rej, sig=(4.0, 3.0), shiftx=sx, shifty=sy,
                                   max_thread=8, max_number_of_rows=H, resident_rows=(lo, hi + 1))
@@ -711,7 +759,7 @@ def main_config(args):
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         stage[:] += (t1 - t0, t2 - t1, t3 - t2)
-        out["sx"], out["sy"] = sx, sy
+        out["sx"], out["sy"], out["q"] = sx, sy, q
 
     stage_keep = []         # the queued calls' descriptors (their arrays) stay alive until collected
     # the stack's own stream: step k's stack kernel (it needs step k's shifts, so it is queued once the
@@ -735,6 +783,9 @@ def main_config(args):
         stage_keep.clear()
         kms.append(ctx.stats().kernel_ms)
         kms = kms[1:]   # the first entry described a warm-up call
+    if args.dump_outputs:       # 1 GPU: the last step's image, its shifts and quality, one step's counters
+        dump_outputs(args.dump_outputs, device_u16(out_img), shiftx=out["sx"], shifty=out["sy"], quality=out["q"],
+                     rejected=np.asarray(rej_all, dtype=np.float64) / args.steps)
     reg_ok = bool(np.array_equal(out["sx"], ex) and np.array_equal(out["sy"], ey))
     kavg = sum(kms) / len(kms)
     stack_bytes = N * C * (e - b) * W * 2 + C * (e - b) * W * 2
@@ -808,7 +859,7 @@ def main_config(args):
             res["roofline"], res["register_roofline"] = sr, rr
         if S & (S - 1):
             res["cpu_baseline_note"] = "none: the oracle's radix-2 DFT takes power-of-two sides only"
-        if not args.no_cpu_baseline and world == 1 and (S & (S - 1)) == 0:
+        if args.cpu_baseline and world == 1 and (S & (S - 1)) == 0:
             res["cpu_baseline"] = cpu_baseline_config(args, args.workload, N, C, H, W, S, layer)
         print(json.dumps(res), flush=True)
     ctx.close()
@@ -846,7 +897,7 @@ def main_sum(args):
             def step():
                 rc, out, _, maxim = ctx.stack_seq(desc, seq)
                 assert rc == 0, ctx.error()
-                res_out["out"] = out
+                res_out["out"], res_out["maxim"] = out, maxim
 
             elapsed = timed(args.steps, args.warmup, step, D)
     res = {
@@ -858,7 +909,9 @@ def main_sum(args):
         "config": {"workload": f"stack_summing {N}x{H}x{W} u16 mono FITS (BASELINE configs[0]), host-pull from "
                                f"files (reads + decode + PCIe + kernels)", "parallelism": "1 GPU"},
     }
-    if not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res_out["out"], maximum=[res_out["maxim"]])
+    if args.cpu_baseline:
         import oracle_lib as orc
         rc, ref, _ = orc.stack_sum(frames, sx, sy)
         res["matches_oracle"] = bool(np.array_equal(res_out["out"], ref))
@@ -916,13 +969,15 @@ def main_register_file(args):
                 torch.cuda.synchronize()
                 t3 = time.perf_counter()
                 stage[:] += (t1 - t0, t2 - t1, t3 - t2)
-                got["sx"], got["sy"] = sx, sy
+                got["sx"], got["sy"], got["q"] = sx, sy, q
 
             for _ in range(args.warmup):
                 step()
             stage[:] = 0
             elapsed = timed(args.steps, 0, step, D)
     stage /= args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, device_u16(out), shiftx=got["sx"], shifty=got["sy"], quality=got["q"])
     file_bytes = N * H * W * 2
     res = {
         "metric": "frames/sec registered + mean-stacked, end to end from a SER file",

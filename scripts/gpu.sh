@@ -7,7 +7,8 @@
 #   test[=K]                    pytest -m gpu (optionally -k K), per-test timeout 200 s
 #   testall[=K]                 the same, going on past assertion failures (at most 8)
 #   smoke                       __graft_entry__.smoke()
-#   bench=NAME[:ARGS]           python bench.py ARGS -> NAME.log + one summary line
+#   bench=NAME[:ARGS]           python bench.py ARGS -> NAME.log + one summary line (--full among ARGS
+#                               for the CPU baseline and, at N GPUs, the strong form after the weak one)
 #   env=NAME:VAR=V[;VAR=V]:ARGS the same with an environment (A/B: SG_* knobs, SG_LIB_PATH)
 #   prof=NAME[:ARGS]            rocprofv3 --kernel-trace --stats of bench.py ARGS -> NAME/
 #   pmc=NAME[@K1,K2][:ARGS]     FETCH_SIZE and WRITE_SIZE passes (own runs) -> NAME_traffic.json

@@ -1,6 +1,6 @@
 """ctypes binding of the CPU oracle (oracle/build/liboracle.so).
 
-TEST INFRASTRUCTURE ONLY: used by tests/, __graft_entry__.smoke() and bench.py's
+TEST INFRASTRUCTURE ONLY: used by tests/, __graft_entry__.smoke() and bench.py --full's
 cpu_baseline leg as the checker / CPU baseline, never by the product path.
 Parity unpinned: see oracle/oracle.h.
 """
