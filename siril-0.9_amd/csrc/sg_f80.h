@@ -9,7 +9,7 @@
  * slow path, which replays GSL's recurrences through this type so its sigma is
  * bit-identical to the reference's.  Only normal numbers and zero are needed (inputs
  * are u16 samples, counts and their squares).  Checked against native long double by
- * tests/test_f80.py.
+ * test_f80_soft_float_matches_x87 (a stand-alone host program, in the CPU suite under tests/).
  */
 #ifndef SG_F80_H
 #define SG_F80_H

@@ -10,7 +10,9 @@
  * multiple of u and every later step adds the even neighbour of t/u.  So two equal
  * consecutive increments are followed by the same increment until a sum would leave the
  * binade (kept one ulp away from the boundary, where the unit changes); there one step is
- * done literally.  Checked against the literal loop by the CPU test suite (tests/).
+ * done literally.  Checked against the literal loop by
+ * test_add_repeat_matches_sequential_loop (a stand-alone host program, in the CPU suite
+ * under tests/), and through the IKSS solver by tests/test_ikss_cpu.py.
  */
 #ifndef SG_REPADD_H
 #define SG_REPADD_H

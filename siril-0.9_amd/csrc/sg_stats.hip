@@ -11,21 +11,23 @@
  *   - k_ikss_hist: layer-0 histogram of the non-zero samples (u16 counter pairs in LDS per
  *     65535-sample chunk, flushed with global atomics) and the maximum over all layers;
  *   - k_ikss_prefix: exclusive prefix counts P[x] = #samples < x;
- *   - k_ikss_solve: one lane per frame runs the IKSS loop on the prefix table: medians are
- *     rank lookups, the MAD is a merge of the two monotone delta sequences on either side
- *     of the median, and the BWMV sums add each distinct value's term count(x) times with
- *     sg_add_repeat (sg_repadd.h), which reproduces the sequential double sum exactly.
+ *   - k_ikss_solve: one lane per frame runs the IKSS loop on the prefix table
+ *     (sg_ikss_frame, sg_ikss.h, host + device): medians are rank lookups, the MAD is a
+ *     merge of the two monotone delta sequences on either side of the median, and the BWMV
+ *     sums add each distinct value's term count(x) times with sg_add_repeat (sg_repadd.h),
+ *     which reproduces the sequential double sum exactly.
  * All double expressions are written as the reference writes them (no contraction), so
- * location / scale equal the reference's bit for bit (tests/test_gpu_stats.py against the
- * CPU restatement in tests/).
+ * location / scale equal the reference's bit for bit: the solver alone on the host
+ * (tests/test_ikss_cpu.py), the three kernels and both entry points on the device
+ * (tests/test_gpu_stats.py), each against the CPU restatement of statistics().
  */
 #include "sg_common.hpp"
 #include "sg_ctx.hpp"
-#include "sg_repadd.h"
+#include "sg_ikss.h"
 #include <math.h>
 #include <vector>
 
-#define SG_ST_BINS 65536
+#define SG_ST_BINS SG_IK_BINS
 #define SG_ST_CHUNK 65535	/* samples per histogram workgroup: the u16 LDS counters cannot wrap */
 
 /* layer-0 histogram of frame blockIdx.y's non-zero samples into hist[x * nf + f] (frame-minor:
@@ -83,187 +85,17 @@ __global__ void __launch_bounds__(64) k_ikss_prefix(uint32_t *__restrict__ hist,
 	hist[(size_t)SG_ST_BINS * nf + f] = run;
 }
 
-struct SgIk {
-	const uint32_t *P;
-	int nf, f;
-	double norm;
-};
-
-__device__ __forceinline__ uint32_t ik_P(const SgIk &k, int x) {
-	return k.P[(size_t)x * k.nf + k.f];
-}
-__device__ __forceinline__ double ik_val(const SgIk &k, int x) {
-	return (double)x / k.norm;	/* newdata[i] = (double) data[i] / ((double) hist_size - 1) (:281) */
-}
-/* value of the sample at rank r (0-based, sorted non-zero samples) */
-__device__ int ik_x_at(const SgIk &k, uint32_t r) {
-	int lo = 1, hi = SG_ST_BINS - 1;
-	while (lo < hi) {
-		const int mid = (lo + hi) >> 1;
-		if (ik_P(k, mid + 1) > r)
-			hi = mid;
-		else
-			lo = mid + 1;
-	}
-	return lo;
-}
-/* samples of value x among ranks [i, j) */
-__device__ __forceinline__ uint32_t ik_cnt(const SgIk &k, int x, uint32_t i, uint32_t j) {
-	uint32_t a = ik_P(k, x), b = ik_P(k, x + 1);
-	a = a > i ? a : i;
-	b = b < j ? b : j;
-	return b > a ? b - a : 0u;
-}
-/* gsl_stats_median_from_sorted_data(data + i, 1, j - i) */
-__device__ double ik_median(const SgIk &k, uint32_t i, uint32_t j) {
-	const uint32_t n = j - i, lhs = i + (n - 1) / 2, rhs = i + n / 2;
-	const double a = ik_val(k, ik_x_at(k, lhs));
-	if (lhs == rhs)
-		return a;
-	return (a + ik_val(k, ik_x_at(k, rhs))) / 2.0;
-}
-/* siril_stats_double_mad (:82-100): median of |data - m| over ranks [i, j) */
-__device__ double ik_mad(const SgIk &k, uint32_t i, uint32_t j, double m) {
-	const uint32_t n = j - i, rl = (n - 1) / 2, rr = n / 2;
-	const int xi = ik_x_at(k, i), xj = ik_x_at(k, j - 1);
-	int lo_b = xi, hi_b = xj + 1;	/* first x with val(x) >= m */
-	while (lo_b < hi_b) {
-		const int mid = (lo_b + hi_b) >> 1;
-		if (ik_val(k, mid) >= m)
-			hi_b = mid;
-		else
-			lo_b = mid + 1;
-	}
-	int hi = lo_b, lo = lo_b - 1;
-	uint32_t seen = 0;
-	double vl = 0.0, vr = 0.0;
-	bool have_l = false;
-	for (;;) {
-		while (lo >= xi && ik_cnt(k, lo, i, j) == 0)
-			lo--;
-		while (hi <= xj && ik_cnt(k, hi, i, j) == 0)
-			hi++;
-		bool take_hi;
-		if (lo < xi)
-			take_hi = true;
-		else if (hi > xj)
-			take_hi = false;
-		else
-			take_hi = fabs(ik_val(k, hi) - m) <= fabs(ik_val(k, lo) - m);
-		const int x = take_hi ? hi : lo;
-		const double d = fabs(ik_val(k, x) - m);
-		const uint32_t c = ik_cnt(k, x, i, j);
-		if (!have_l && rl < seen + c) {
-			vl = d;
-			have_l = true;
-		}
-		if (rr < seen + c) {
-			vr = d;
-			break;
-		}
-		seen += c;
-		if (take_hi)
-			hi++;
-		else
-			lo--;
-	}
-	return rl == rr ? vl : (vl + vr) / 2.0;
-}
-/* siril_stats_double_bwmv (:128-150) over the sorted ranks [i, j) */
-__device__ double ik_bwmv(const SgIk &k, uint32_t i, uint32_t j, double mad, double median) {
-	double bwmv = 0.0, up = 0.0, down = 0.0;
-	if (mad > 0.0) {
-		const int xi = ik_x_at(k, i), xj = ik_x_at(k, j - 1);
-		for (int x = xi; x <= xj; x++) {
-			const uint32_t c = ik_cnt(k, x, i, j);
-			if (!c)
-				continue;
-			const double d = ik_val(k, x);
-			const double yi = (d - median) / (9 * mad);
-			const double yi2 = yi * yi;
-			const double ai = (fabs(yi) < 1.0) ? 1.0 : 0.0;
-			const double tu = ai * ((d - median) * (d - median)) * (((1 - yi2) * (1 - yi2)) * ((1 - yi2) * (1 - yi2)));
-			const double td = (ai * (1 - yi2) * (1 - 5 * yi2));
-			up = sg_add_repeat(up, tu, c);
-			down = sg_add_repeat(down, td, c);
-		}
-		bwmv = (double)(j - i) * (up / (down * down));
-	}
-	return bwmv;
-}
-
-/* IKSS (:152-187), one lane per frame; rc[f] = -1 when the frame has no non-zero sample */
+/* IKSS (sg_ikss.h), one lane per frame; rc[f] = -1 when the frame has no non-zero sample */
 __global__ void __launch_bounds__(64)
 k_ikss_solve(const uint32_t *__restrict__ P, const uint32_t *__restrict__ maxi, int nf, double *__restrict__ out,
 		int *__restrict__ rc) {
 	const int f = blockIdx.x * 64 + threadIdx.x;
 	if (f >= nf)
 		return;
-	SgIk k;
-	k.P = P;
-	k.nf = nf;
-	k.f = f;
-	k.norm = maxi[f] <= 255u ? 255.0 : 65535.0;	/* get_normalized_value, src/core/utils.c:454-459 */
-	const uint32_t n = ik_P(k, SG_ST_BINS);
-	double location = 0.0, scale = 0.0;
-	int r = 0;
-	if (!n) {
-		r = -1;	/* ngoodpix == 0: statistics() returns NULL (:249-252) */
-	} else {
-		uint32_t i = 0, j = n;
-		double s0 = 1;
-		for (int guard = 0;; guard++) {
-			if (guard > 10000) {
-				r = -2;	/* no convergence (the reference would loop) */
-				break;
-			}
-			if (j - i < 1) {
-				location = scale = 0;
-				break;
-			}
-			const double m = ik_median(k, i, j);
-			const double mad = ik_mad(k, i, j, m);
-			const double s = sqrt(ik_bwmv(k, i, j, mad, m));
-			if (s < 2E-23) {
-				location = m;
-				scale = 0;
-				break;
-			}
-			if (((s0 - s) / s) < 10E-6) {
-				location = m;
-				scale = 0.991 * s;
-				break;
-			}
-			s0 = s;
-			const double xlow = m - 4 * s, xhigh = m + 4 * s;
-			/* while (data[i] < xlow) i++: first x with val(x) >= xlow */
-			int lo = 1, hi = SG_ST_BINS;
-			while (lo < hi) {
-				const int mid = (lo + hi) >> 1;
-				if (ik_val(k, mid) >= xlow)
-					hi = mid;
-				else
-					lo = mid + 1;
-			}
-			const uint32_t ni = ik_P(k, lo);
-			i = ni > i ? ni : i;
-			/* while (data[j - 1] > xhigh) j--: last x with val(x) <= xhigh */
-			lo = 0;
-			hi = SG_ST_BINS - 1;
-			while (lo < hi) {
-				const int mid = (lo + hi + 1) >> 1;
-				if (ik_val(k, mid) <= xhigh)
-					lo = mid;
-				else
-					hi = mid - 1;
-			}
-			const uint32_t nj = ik_P(k, lo + 1);
-			j = nj < j ? nj : j;
-		}
-	}
-	out[2 * f] = location * k.norm;	/* back to the original range (:286-288) */
-	out[2 * f + 1] = scale * k.norm;
-	rc[f] = r;
+	double location, scale;
+	rc[f] = sg_ikss_frame(P, nf, f, maxi[f], &location, &scale);
+	out[2 * f] = location;
+	out[2 * f + 1] = scale;
 }
 
 extern "C" int sg_frame_stats_ikss_device(sg_ctx *ctx, int dev_index, const uint16_t *d_frames, int nframes, int C,

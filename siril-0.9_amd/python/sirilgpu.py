@@ -497,6 +497,17 @@ class Context:
                                                  ctypes.c_void_p(stream) if stream else None)
         return rc, loc, scl
 
+    def frame_stats_ikss_host(self, frames):
+        """the same statistics of host frames [N][C][H][W] u16 (sg_frame_stats_ikss);
+        returns (rc, location[N], scale[N])"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        N, C, H, W = frames.shape
+        loc = np.zeros(N, dtype=np.float64)
+        scl = np.zeros(N, dtype=np.float64)
+        rc = self.lib.sg_frame_stats_ikss(self.ctx, frames.ctypes.data_as(ctypes.c_void_p), N, C, H, W,
+                                          loc.ctypes.data_as(ctypes.c_void_p), scl.ctypes.data_as(ctypes.c_void_p))
+        return rc, loc, scl
+
     def warp(self, image, hom, out_size=None, interpolation=OPENCV_LINEAR):
         """cvTransformImage on a memory-order image [C][H][W]; hom = the 3x3 homography
         (Homography h00..h22), out_size = (ref.x, ref.y)"""

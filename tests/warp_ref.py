@@ -4,6 +4,8 @@ warpPerspective (imgwarp.cpp, BORDER_CONSTANT 0, no WARP_INVERSE_MAP) on the fli
 available here and its version is unpinned, so this pins the GPU kernel to the published
 algorithm (float32 coefficient tables, float32 sums in OpenCV's order), not to an OpenCV
 build: parity unpinned."""
+import functools
+
 import numpy as np
 
 F = np.float32
@@ -49,6 +51,7 @@ def coeffs(interp, x):
     return [F(v * tot) for v in k]
 
 
+@functools.lru_cache(maxsize=None)
 def table(interp):
     K = {1: 2, 3: 4, 4: 8}[interp]
     t1 = [coeffs(interp, F(i) * F(1.0 / 32)) for i in range(32)]
@@ -61,15 +64,19 @@ def table(interp):
     return tab, K
 
 
-def warp(img, hom, out_size=None, interp=1):
+def warp(img, hom, out_size=None, interp=1, bw=None, return_sums=False):
+    """bw forces the column-block width (OpenCV's is min(1024 / min(16, oH), oW): the x
+    association of the coordinate sums); return_sums also returns the float32 sums before
+    saturate_cast<ushort>, [C][oH][oW] in memory order like the image"""
     img = np.asarray(img, dtype=np.uint16)
     C, H, W = img.shape
     oW, oH = out_size if out_size else (W, H)
     if interp == 2:
         interp = 1
     M = invert3(hom)
-    bh0 = min(16, oH)
-    bw = max(1, min(1024 // bh0, oW))
+    if bw is None:
+        bh0 = min(16, oH)
+        bw = max(1, min(1024 // bh0, oW))
     yd, x = np.meshgrid(np.arange(oH, dtype=np.float64), np.arange(oW, dtype=np.float64), indexing="ij")
     xb = np.floor(x / bw) * bw
     x1 = x - xb
@@ -86,6 +93,7 @@ def warp(img, hom, out_size=None, interp=1):
         return v, ok
 
     out = np.zeros((C, oH, oW), dtype=np.uint16)
+    sums = np.zeros((C, oH, oW), dtype=np.float32)
     with np.errstate(divide="ignore", invalid="ignore"):
         if interp == 0:
             Wi = np.where(Wd != 0, 1.0 / Wd, 0.0)
@@ -94,7 +102,8 @@ def warp(img, hom, out_size=None, interp=1):
             for c in range(C):
                 v, ok = src(c, X, Y)
                 out[c] = v.astype(np.uint16)[::-1]
-            return out
+                sums[c] = v[::-1]
+            return (out, sums) if return_sums else out
         tab, K = table(interp)
         Wi = np.where(Wd != 0, 32.0 / Wd, 0.0)
         X = np.rint(np.clip((X0 + M[0] * x1) * Wi, INT_MIN, INT_MAX)).astype(np.int64)
@@ -127,4 +136,5 @@ def warp(img, hom, out_size=None, interp=1):
             v = np.clip(r, 0, 65535).astype(np.uint16)
             v[allout] = 0
             out[c] = v[::-1]
-    return out
+            sums[c] = np.where(allout, F(0), s.astype(np.float32))[::-1]
+    return (out, sums) if return_sums else out
