@@ -53,6 +53,7 @@ __global__ void k_synth_fill(uint16_t *frames, int first_frame, int nframes, int
 		int row_end, uint64_t seed, int maxshift, int64_t frame_stride, int64_t plane_stride);
 
 #include "sg_ctx.hpp"
+#include "sg_stack_plan.hpp"
 
 __global__ void k_flip_rows(const uint16_t *src, uint16_t *dst, int W, int rows);
 __global__ void k_stage_copy(uint4 *dst, const uint4 *src, unsigned int n16);
@@ -215,131 +216,97 @@ extern "C" int sg_device_count(const sg_ctx *ctx, int *ndev) {
 	return SG_OK;
 }
 
-/* ---- reference block partition (src/stacking/stacking.c:1397-1476) and the libgomp
- *      schedule(static) assignment of blocks to OpenMP threads (:1513-1516) ---- */
-struct Block {
-	long channel, start_row, end_row;
-};
+/* ---- kernel lookup tables: one per templated family, naming exactly the instantiations the
+ *      .hip files define (an entry without one would leave the library unloadable); a null
+ *      entry is a case no kernel exists for ---- */
+typedef void (*SgHistFn)(SgStackParams, const int *, const int4 *, unsigned int *, unsigned int *);
+typedef void (*SgSortedFn)(SgStackParams, const unsigned int *, const unsigned int *);
+typedef void (*SgReduce3Fn)(SgStackParams, const int *, const int *);
+typedef void (*SgLinfitFn)(SgStackParams, unsigned int *, unsigned int *);
+typedef void (*SgReplayFn)(SgStackParams);
 
-static int make_blocks(long H, int nb_channels, int max_number_of_rows, int nb_threads,
-		std::vector<Block> &blocks) {
-	int size_of_stacks = max_number_of_rows / nb_threads;
-	if (size_of_stacks == 0)
-		size_of_stacks = 1;
-	long nb_parallel_stacks;
-	int remainder;
-	if (H / size_of_stacks < 4) {
-		nb_parallel_stacks = 4 * nb_channels;
-		size_of_stacks = (int)(H / 4);
-		remainder = (int)(H % 4);
-	} else {
-		nb_parallel_stacks = H * nb_channels / size_of_stacks;
-		if (nb_parallel_stacks % nb_channels != 0 || (H * nb_channels) % size_of_stacks != 0) {
-			nb_parallel_stacks += nb_channels - (nb_parallel_stacks % nb_channels);
-			size_of_stacks = (int)(H * nb_channels / nb_parallel_stacks);
-		}
-		remainder = (int)(H - (nb_parallel_stacks / nb_channels * size_of_stacks));
-	}
-	if (size_of_stacks <= 0)
-		return -1;
-	blocks.clear();
-	long channel = 0, row = 0, end;
-	do {
-		if ((long)blocks.size() >= nb_parallel_stacks)
-			return -1;
-		Block b;
-		b.channel = channel;
-		b.start_row = row;
-		end = row + size_of_stacks - 1;
-		if (remainder > 0) {
-			end++;
-			remainder--;
-		}
-		if (end >= H - 1 || (H - end < size_of_stacks / 10)) {
-			end = H - 1;
-			row = 0;
-			channel++;
-			remainder = (int)(H - (nb_parallel_stacks / nb_channels * size_of_stacks));
-		} else {
-			row = end + 1;
-		}
-		b.end_row = end;
-		blocks.push_back(b);
-	} while (channel < nb_channels);
-	return (long)blocks.size() == nb_parallel_stacks ? 0 : -1;
+/* k_stack_hist<REJ, NORM, NI>: rows REJ = 1 PERCENTILE, 2 SIGMA, 3 SIGMEDIAN, 4 WINSORIZED, 8 stack_median */
+static constexpr int SG_HIST_REJ[5] = {1, 2, 3, 4, 8};
+#define SG_HIST_ROW(R) {{k_stack_hist<R, 0, 1>, nullptr}, {k_stack_hist<R, 1, 1>, nullptr}, \
+		{k_stack_hist<R, 2, 1>, nullptr}, {k_stack_hist<R, 3, 1>, nullptr}}
+#define SG_HIST_ROW2(R) {{k_stack_hist<R, 0, 1>, k_stack_hist<R, 0, 2>}, {k_stack_hist<R, 1, 1>, nullptr}, \
+		{k_stack_hist<R, 2, 1>, nullptr}, {k_stack_hist<R, 3, 1>, nullptr}}
+static constexpr SgHistFn SG_HIST_KERNELS[5][4][2] = {	/* [REJ row][NORM][NI - 1] */
+	SG_HIST_ROW(1), SG_HIST_ROW2(2), SG_HIST_ROW(3), SG_HIST_ROW2(4), SG_HIST_ROW(8)};
+#undef SG_HIST_ROW
+#undef SG_HIST_ROW2
+
+#define SG_SORTED_ROW(R) {k_stack_sorted<R, false>, k_stack_sorted<R, true>}
+static constexpr SgSortedFn SG_SORTED_KERNELS[5][2] = {	/* [log2 NREG][LISTED] */
+	SG_SORTED_ROW(1), SG_SORTED_ROW(2), SG_SORTED_ROW(4), SG_SORTED_ROW(8), SG_SORTED_ROW(16)};
+#undef SG_SORTED_ROW
+
+#define SG_R3_ROW(M) {k_stack_reduce3<M, 1>, k_stack_reduce3<M, 2>, k_stack_reduce3<M, 4>}
+static constexpr SgReduce3Fn SG_REDUCE3_KERNELS[5][3] = {	/* [M][log2 SEG] */
+	SG_R3_ROW(0), SG_R3_ROW(1), SG_R3_ROW(2), SG_R3_ROW(3), SG_R3_ROW(4)};
+#undef SG_R3_ROW
+
+static constexpr SgLinfitFn SG_LINFIT_KERNELS[2][3][2] = {	/* [KM / 16][log2 (NW / 4)][PAIR] */
+	{{k_stack_linfit<8, 4, false>, k_stack_linfit<8, 4, true>}, {k_stack_linfit<8, 8, false>, k_stack_linfit<8, 8, true>},
+		{k_stack_linfit<8, 16, false>, nullptr}},
+	{{k_stack_linfit<16, 4, false>, k_stack_linfit<16, 4, true>}, {k_stack_linfit<16, 8, false>, k_stack_linfit<16, 8, true>},
+		{nullptr, nullptr}}};
+
+static constexpr SgReplayFn SG_REPLAY_KERNELS[2] = {k_stack_replay<512>, k_stack_replay<SG_REPLAY_MAXN>};	/* [N > 512] */
+
+static int log2_index(int v, int n) {	/* i with v == 1 << i below n, else -1 */
+	for (int i = 0; i < n; i++)
+		if (v == 1 << i)
+			return i;
+	return -1;
 }
 
-static void omp_static_chunk(long n, int nthr, int t, long *begin, long *end) {
-	long q = n / nthr, r = n % nthr;
-	if (t < r) {
-		q++;
-		*begin = q * t;
-	} else {
-		*begin = q * t + r;
-	}
-	*end = *begin + q;
+static const void *hist_kernel(const SgStackPlan &pl) {
+	for (int r = 0; r < 5; r++)
+		if (SG_HIST_REJ[r] == pl.rj && pl.norm >= 0 && pl.norm < 4 && pl.ni >= 1 && pl.ni <= 2)
+			return (const void *)SG_HIST_KERNELS[r][pl.norm][pl.ni - 1];
+	return nullptr;
 }
 
-static int default_threads(void) {
-	long n = sysconf(_SC_NPROCESSORS_ONLN);
-	return n > 0 ? (int)n : 1;
-}
-
-static int pick_nreg(int N) {
-	if (N <= 64) return 1;
-	if (N <= 128) return 2;
-	if (N <= 256) return 4;
-	if (N <= 512) return 8;
-	if (N <= 1024) return 16;
-	return 0;
+static const void *linfit_kernel(const SgStackPlan &pl) {
+	const int w = log2_index(pl.nw / 4, 3);
+	return (pl.km == 8 || pl.km == 16) && w >= 0 ? (const void *)SG_LINFIT_KERNELS[pl.km / 16][w][pl.pair ? 1 : 0] : nullptr;
 }
 
 static hipError_t launch_sorted(int nreg, bool listed, dim3 grid, size_t lds, hipStream_t s, const SgStackParams &p,
 		const unsigned int *list, const unsigned int *list_count) {
-	switch (nreg * 2 + (listed ? 1 : 0)) {
-#define SG_CASE(R, LI)                                                                              \
-	case R * 2 + LI:                                                                            \
-		(void)hipFuncSetAttribute((const void *)k_stack_sorted<R, LI>,                      \
-				hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);              \
-		hipLaunchKernelGGL((k_stack_sorted<R, LI>), grid, dim3(SG_SORT_THREADS), lds, s, p, list,  \
-				list_count);                                                        \
-		return hipGetLastError();
-		SG_CASE(1, 0)
-		SG_CASE(1, 1)
-		SG_CASE(2, 0)
-		SG_CASE(2, 1)
-		SG_CASE(4, 0)
-		SG_CASE(4, 1)
-		SG_CASE(8, 0)
-		SG_CASE(8, 1)
-		SG_CASE(16, 0)
-		SG_CASE(16, 1)
-#undef SG_CASE
-	}
-	return hipErrorInvalidValue;
+	const int r = log2_index(nreg, 5);
+	if (r < 0)
+		return hipErrorInvalidValue;
+	const void *kf = (const void *)SG_SORTED_KERNELS[r][listed ? 1 : 0];
+	(void)hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	void *args[] = {(void *)&p, &list, &list_count};
+	return hipLaunchKernel(kf, grid, dim3(SG_SORT_THREADS), args, lds, s);
 }
 
-/* k_stack_literal: one thread per queued pixel with N * 5 bytes of scratch each; SG_LIT_THREADS
- * threads up to 2048 frames, then as many as 1 GiB of scratch holds (at least 4096) */
-static unsigned lit_thread_count(int N) {
-	const size_t lit_bytes = ((size_t)N * 5 + 15) & ~(size_t)15;
-	return (unsigned)std::max<size_t>(4096, std::min<size_t>(SG_LIT_THREADS, ((size_t)1 << 30) / lit_bytes) & ~(size_t)63);
-}
-static size_t lit_scratch_bytes(int N) {
-	return (size_t)lit_thread_count(N) * (((size_t)N * 5 + 15) & ~(size_t)15);
-}
 
 /* SUM over row bands streamed by the host-pull path: the raw sums and the maximum carry
  * across the band calls, the scaling runs once after the last band */
 enum { SUM_WHOLE = 0, SUM_FIRST_BAND = 1, SUM_MID_BAND = 2, SUM_LAST_BAND = 3 };
 
-/* counter block of one slot: rejection shards, then {flag count, walk fault, redo count, compact
- * count, loop fault} and the SUM maximum 64 bytes further */
+/* counter block of one slot: rejection shards (SG_CTR_REJB), then the flag words below */
 static const size_t SG_CTRB = SG_CTR_REJB + 128;
-/* host-mapped slot k_ctr_finalize writes: rejection sums at 0, the flag block at 64 */
+/* host-mapped slot k_ctr_finalize writes: rejection sums at 0, the flag words at 64 */
 static const size_t SG_CTR_HOSTB = 256;
-/* blocks of the listed k_stack_sorted launches (grid-stride over any list length) */
-#define SG_LIST_GRID 1024
+/* the flag words (unsigned int) of a counter block, on the device and in the host copy */
+enum SgFlagWord {
+	SG_FL_SLOW = 0,		/* flag count: pixels queued for the replay / literal kernels */
+	SG_FL_WALK_FAULT = 1,	/* a stale-state chain needs rows that are not resident */
+	SG_FL_REDO = 2,		/* redo count of the histogram / linfit kernels */
+	SG_FL_COMPACT = 3,	/* compact columns taken */
+	SG_FL_LOOP_FAULT = 4,	/* a SIGMEDIAN pixel's reference loop never ends */
+	SG_FL_EXPORT = 6,	/* exported WINSORIZED columns */
+	SG_FL_VERDICT = 7,	/* k_norm_fma_check's load verdict */
+	SG_FL_SUM_MAX = 16	/* SUM maximum (byte 64: kept across the bands of a streamed SUM) */
+};
+static unsigned int *flag_words(void *ctr_block) {
+	return (unsigned int *)((char *)ctr_block + SG_CTR_REJB);
+}
 
 /*
  * wait for the call queued in counter slot `slot` and take its results: faults, the rejection
@@ -357,23 +324,23 @@ static int stack_fold(sg_ctx *ctx, SgDevice &dv, int slot, uint64_t rej[3][2], u
 	HIPCHK(hipEventElapsedTime(&ms2, dv.cev[slot][0], dv.cev[slot][2]));
 	st.kernel_ms = ms;
 	st.total_ms = ms2;
-	st.slow_pixels = fl[0];
+	st.slow_pixels = fl[SG_FL_SLOW];
 	if (st.path == 1)
-		st.chain_pixels = fl[2];
-	st.compact_pixels = std::min<uint64_t>(fl[3], st.compact_pixels);	/* pstats holds the capacity */
-	st.exported_pixels = st.exported_pixels ? std::min<uint64_t>(fl[6], st.exported_pixels) : 0;	/* capacity, as compact */
+		st.chain_pixels = fl[SG_FL_REDO];
+	st.compact_pixels = std::min<uint64_t>(fl[SG_FL_COMPACT], st.compact_pixels);	/* pstats holds the capacity */
+	st.exported_pixels = st.exported_pixels ? std::min<uint64_t>(fl[SG_FL_EXPORT], st.exported_pixels) : 0;	/* capacity, as compact */
 	if (st.norm_fma > 0)	/* k_norm_fma_check's verdict, read back beside the counters (the launch set the best allowed) */
-		st.norm_fma = st.norm_fma == 2 && !(fl[7] & 2u) ? 2 : (fl[7] & 1u) ? 0 : 1;
+		st.norm_fma = st.norm_fma == 2 && !(fl[SG_FL_VERDICT] & 2u) ? 2 : (fl[SG_FL_VERDICT] & 1u) ? 0 : 1;
 	if (sync) {	/* the calling stack_device_core publishes dv.stats when it returns */
 		dv.stats = st;
 	} else {
 		std::lock_guard<std::mutex> lk(ctx->mu);
 		ctx->stats = st;
 	}
-	if (fl[4])
+	if (fl[SG_FL_LOOP_FAULT])
 		return set_err(ctx, SG_ERR_GENERIC, "SIGMEDIAN: the reference's clipping loop never ends for some pixel "
 				"(a pass replaces samples by the values they already hold, stacking.c:1696-1709)%s%.0ld", "", 0);
-	if (fl[1])
+	if (fl[SG_FL_WALK_FAULT])
 		return set_err(ctx, SG_ERR_WALK, "a first-pass early break needs the stale rejected[] of a pixel "
 				"whose frame rows are not resident; make the full frames resident%s%.0ld", "", 0);
 	if (rej) {
@@ -384,7 +351,7 @@ static int stack_fold(sg_ctx *ctx, SgDevice &dv, int slot, uint64_t rej[3][2], u
 		}
 	}
 	if (maxim_out)
-		*maxim_out = dv.pend_sum_read[slot] ? fl[16] : 0;
+		*maxim_out = dv.pend_sum_read[slot] ? fl[SG_FL_SUM_MAX] : 0;
 	return SG_OK;
 }
 
@@ -404,6 +371,392 @@ static void stack_fold_acc(sg_ctx *ctx, SgDevice &dv, int slot) {
 	dv.acc_max = std::max<uint64_t>(dv.acc_max, mx);
 }
 
+/* ---- the launch step of a stacking call: everything that touches the device, driven by the
+ *      plan (sg_stack_plan.hpp) alone ---- */
+struct StackCall {
+	sg_ctx *ctx;
+	SgDevice *dv;
+	int slot;		/* counter slot and its buffers */
+	SgSlot *sb;
+	hipStream_t s, ts;	/* the call's stream; the stream of everything after the main kernel */
+	SgStackParams p;
+	SgChainTables ct;
+	unsigned int *fl;	/* the slot's flag words on the device */
+	unsigned int *redo_list;
+};
+
+/* the counter slot (and its buffers): a synchronous call uses slot 0 (a streamed SUM keeps its
+ * maximum there), an async call the free slot, folding the older pending call when both are taken */
+static int choose_slot(sg_ctx *ctx, SgDevice &dv, bool async) {
+	if (!async) {
+		if (dv.pend[0])
+			stack_fold_acc(ctx, dv, 0);
+		return 0;
+	}
+	if (dv.pend[0] && dv.pend[1])
+		stack_fold_acc(ctx, dv, dv.pend_seq[0] < dv.pend_seq[1] ? 0 : 1);
+	return dv.pend[0] ? 1 : 0;
+}
+
+/* counters: rejection shards, then the flag words; one memset, one read-back.  They are zero
+ * when the slot's last call finished (k_ctr_finalize); a fresh or failed slot is cleared here
+ * (SUM keeps its maximum across the bands of a streamed sum) */
+static int prepare_counters(StackCall &c, const SgStackPlan &pl, int sum_mode) {
+	sg_ctx *ctx = c.ctx;
+	SgDevice &dv = *c.dv;
+	const void *old_ctr = dv.ctr.p;
+	HIPCHK(ensure(dv.ctr, 2 * SG_CTRB));
+	if (dv.ctr.p != old_ctr)
+		dv.ctr_clean[0] = dv.ctr_clean[1] = false;
+	if (!dv.ctr_h) {
+		HIPCHK(hipHostMalloc(&dv.ctr_h, 2 * SG_CTR_HOSTB, hipHostMallocMapped | hipHostMallocCoherent));
+		HIPCHK(hipHostGetDevicePointer((void **)&dv.ctr_hd, dv.ctr_h, 0));
+	}
+	char *cblk = (char *)dv.ctr.p + (size_t)c.slot * SG_CTRB;
+	c.fl = flag_words(cblk);
+	const bool clear_max = sum_mode == SUM_WHOLE || sum_mode == SUM_FIRST_BAND;
+	if (!dv.ctr_clean[c.slot])
+		HIPCHK(hipMemsetAsync(cblk, 0, clear_max ? SG_CTRB : SG_CTR_REJB + SG_FL_SUM_MAX * sizeof(unsigned int), c.s));
+	else if (clear_max && pl.sum)
+		HIPCHK(hipMemsetAsync(c.fl + SG_FL_SUM_MAX, 0, sizeof(unsigned int), c.s));
+	dv.ctr_clean[c.slot] = false;
+	c.p.rej = (unsigned long long *)cblk;
+	c.p.flag_count = c.fl + SG_FL_SLOW;
+	c.p.walk_fault = c.fl + SG_FL_WALK_FAULT;
+	c.p.loop_fault = c.fl + SG_FL_LOOP_FAULT;
+	c.p.maxim = c.fl + SG_FL_SUM_MAX;
+	return SG_OK;
+}
+
+/* the slot's buffers of a rejection / median stack, grown to the plan's sizes */
+static int prepare_rejection_buffers(StackCall &c, const SgStackPlan &pl) {
+	sg_ctx *ctx = c.ctx;
+	SgSlot &sb = *c.sb;
+	SgStackParams &p = c.p;
+	HIPCHK(ensure(sb.flag_list, sizeof(unsigned int) * pl.npix_launch));
+	/* pixel classes carry this call's epoch (sg_flag_get): no per-call clear; the map is
+	 * cleared when it is new or the 31 epochs wrap */
+	const void *old_map = sb.flag_map.p;
+	HIPCHK(ensure(sb.flag_map, pl.npix_img));
+	if (sb.flag_map.p != old_map || sb.flag_epoch <= 0 || sb.flag_epoch >= 31) {
+		HIPCHK(hipMemsetAsync(sb.flag_map.p, 0, sb.flag_map.size, c.s));
+		sb.flag_epoch = 0;
+	}
+	p.flag_epoch = (unsigned int)++sb.flag_epoch;
+	p.flag_list = (unsigned int *)sb.flag_list.p;
+	p.flag_cap = (unsigned int)pl.npix_launch;
+	p.flag_map = (uint8_t *)sb.flag_map.p;
+	HIPCHK(ensure(sb.scratch, pl.scratch_bytes));
+	if (pl.linfit_tables) {
+		HIPCHK(ensure(sb.lin_tab, sizeof(double) * 2 * ((size_t)pl.N + 1)));
+		p.linfit_tab = (const double *)sb.lin_tab.p;
+	}
+	if (pl.redo != SG_REDO_NONE) {
+		HIPCHK(ensure(sb.redo, sizeof(unsigned int) * (pl.npix_launch + 16)));
+		c.redo_list = (unsigned int *)sb.redo.p + 16;
+	}
+	if (pl.compact) {
+		HIPCHK(ensure(sb.cmp_cols, pl.cmp_cap * (size_t)pl.N * 2));
+		HIPCHK(ensure(sb.cmp_list, pl.cmp_cap * sizeof(unsigned int)));
+		p.cmp_cols = (uint16_t *)sb.cmp_cols.p;
+		p.cmp_list = (unsigned int *)sb.cmp_list.p;
+		p.cmp_count = c.fl + SG_FL_COMPACT;	/* cleared with the counters */
+		p.cmp_cap = (unsigned int)pl.cmp_cap;
+	}
+	if (pl.wexp) {
+		HIPCHK(ensure(sb.wx, pl.wx_cap * (SG_HIST_HROWS + 3) * sizeof(uint32_t)));
+		p.wx = (uint32_t *)sb.wx.p;
+		p.wx_cap = (unsigned int)pl.wx_cap;
+		p.wx_count = c.fl + SG_FL_EXPORT;	/* cleared with the counters */
+		p.wx_kmax = pl.wx_kmax;
+	}
+	return SG_OK;
+}
+
+/* the call's inputs (shift table, normalisation coefficients, chain tables, border-row table)
+ * reach the device in one copy: one pinned host block -> one device block; sets the kernels'
+ * pointers into it */
+static int stage_inputs(StackCall &c, const SgStackPlan &pl) {
+	sg_ctx *ctx = c.ctx;
+	SgSlot &sb = *c.sb;
+	SgStackParams &p = c.p;
+	const int N = pl.N, Npad = pl.Npad;
+	const size_t b_sh = sizeof(int) * pl.sh.size(), o_nm = (b_sh + 255) & ~(size_t)255;
+	const size_t b_nm = sizeof(double) * pl.nm.size(), o_tb = (o_nm + b_nm + 255) & ~(size_t)255;
+	const size_t o_zt = (o_tb + sizeof(int) * pl.tables.size() + 255) & ~(size_t)255;
+	const size_t tot = (o_zt + sizeof(int) * pl.ztab.size() + 15) & ~(size_t)15;
+	if (sb.stage_pending) {	/* an earlier call's copy may still read the host block */
+		HIPCHK(hipEventSynchronize(sb.stage_ev));
+		sb.stage_pending = false;
+	}
+	if (sb.stage_h_size < tot) {
+		if (sb.stage_h)
+			(void)hipHostFree(sb.stage_h);
+		sb.stage_h = nullptr;
+		sb.stage_h_size = 0;
+		/* coherent: the device reads it uncached, so no call sees an earlier call's inputs */
+		HIPCHK(hipHostMalloc(&sb.stage_h, tot, hipHostMallocMapped | hipHostMallocCoherent));
+		sb.stage_h_size = tot;
+		HIPCHK(hipHostGetDevicePointer(&sb.stage_d, sb.stage_h, 0));
+	}
+	HIPCHK(ensure(sb.inb, tot));
+	char *hb = (char *)sb.stage_h;
+	memcpy(hb, pl.sh.data(), b_sh);
+	if (b_nm)
+		memcpy(hb + o_nm, pl.nm.data(), b_nm);
+	if (!pl.tables.empty())
+		memcpy(hb + o_tb, pl.tables.data(), sizeof(int) * pl.tables.size());
+	if (!pl.ztab.empty())
+		memcpy(hb + o_zt, pl.ztab.data(), sizeof(int) * pl.ztab.size());
+	hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(64, (tot / 16 + 255) / 256)), dim3(256), 0, c.s,
+			(uint4 *)sb.inb.p, (const uint4 *)sb.stage_d, (unsigned int)(tot / 16));
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(sb.stage_ev, c.s));
+	sb.stage_pending = true;
+	const char *db = (const char *)sb.inb.p;
+	p.hist_tab = (const int *)db;
+	if (pl.use_shift) {
+		p.shiftx = p.hist_tab + Npad + Npad / 2;
+		p.shifty = p.shiftx + N;
+	}
+	if (pl.normalize) {
+		p.offset = (const double *)(db + o_nm);
+		p.mul = p.offset + N;
+		p.scale = p.offset + 2 * N;
+		p.hist_norm = p.offset + 3 * N;
+	}
+	p.ztab = pl.ztab.empty() ? nullptr : (const int *)(db + o_zt);
+	memset(&c.ct, 0, sizeof c.ct);
+	if (!pl.tables.empty()) {
+		const int *tb = (const int *)(db + o_tb);
+		c.ct.nblocks = pl.nblocks;
+		c.ct.blk_of_row = tb;
+		c.ct.blk_channel = tb + (size_t)pl.C * pl.H;
+		c.ct.blk_start = c.ct.blk_channel + pl.nblocks;
+		c.ct.blk_end = c.ct.blk_start + pl.nblocks;
+		c.ct.blk_first = c.ct.blk_end + pl.nblocks;
+	}
+	return SG_OK;
+}
+
+/* everything after the main kernel runs on ts: the call's stream, or the device's tail stream
+ * for an async call whose result is wanted at sg_stack_collect only (it then overlaps the
+ * next call's main kernel, which uses the other slot's buffers) */
+static int to_tail(StackCall &c, const SgStackPlan &pl, bool async) {
+	sg_ctx *ctx = c.ctx;
+	SgDevice &dv = *c.dv;
+	if (!(async && pl.result_at_collect))
+		return SG_OK;
+	if (!dv.tail) {
+		HIPCHK(hipStreamCreateWithFlags(&dv.tail, hipStreamNonBlocking));
+		HIPCHK(hipEventCreateWithFlags(&dv.tail_ev, hipEventDisableTiming));
+		HIPCHK(hipEventCreateWithFlags(&dv.tail_done_ev, hipEventDisableTiming));
+	}
+	HIPCHK(hipEventRecord(dv.tail_ev, c.s));
+	HIPCHK(hipStreamWaitEvent(dv.tail, dv.tail_ev, 0));
+	c.ts = dv.tail;
+	return SG_OK;
+}
+
+/* A/B (probe builds): report the resident histogram workgroups per CU */
+static void report_hist_occupancy(const StackCall &c, const SgStackPlan &pl) {
+	int per_cu = -1;
+	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)SG_HIST_KERNELS[1][0][pl.ni == 2 ? 1 : 0],
+			sgh_block_threads(pl.ni, 2), (size_t)pl.hist_ldspad);
+	hipDeviceProp_t prop;
+	(void)hipGetDeviceProperties(&prop, c.dv->id);
+	fprintf(stderr, "k_stack_hist: %d workgroups/CU (lds/CU %zu, lds/block max %zu, pad %d)\n", per_cu,
+			(size_t)prop.maxSharedMemoryPerMultiProcessor, (size_t)prop.sharedMemPerBlock, pl.hist_ldspad);
+}
+
+/* the main kernel of a rejection / median stack between the events cev[0] and cev[1] */
+static int launch_rejection_main(StackCall &c, const SgStackPlan &pl) {
+	sg_ctx *ctx = c.ctx;
+	SgStackParams &p = c.p;
+	hipEvent_t *cev = c.dv->cev[c.slot];
+	unsigned int *redo_count = c.fl + SG_FL_REDO;	/* cleared with the counters */
+	if (pl.linfit_tables) {
+		hipLaunchKernelGGL(k_linfit_tables, dim3((pl.N + 64) / 64), dim3(64), 0, c.s, (double *)c.sb->lin_tab.p, pl.N);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(cev[0], c.s));
+	const dim3 grid(pl.main_grid[0]);
+	if (pl.main == SG_MAIN_HIST) {
+		if (SG_DBG(p) == 14)
+			report_hist_occupancy(c, pl);
+		if (pl.norm_check) {
+			hipLaunchKernelGGL(k_norm_fma_check, dim3(16, (unsigned)pl.N), dim3(256), 0, c.s, (double *)p.hist_norm, pl.N,
+					pl.Npad, pl.norm, c.fl + SG_FL_VERDICT);
+			HIPCHK(hipGetLastError());
+		}
+		const void *kf = hist_kernel(pl);
+		if (!kf)
+			return set_err(ctx, SG_ERR_GENERIC, "no histogram kernel for this case%s%.0ld", "", 0);
+		const int4 *norm_pairs = (const int4 *)p.hist_norm;
+		void *args[] = {&p, &p.hist_tab, &norm_pairs, &redo_count, &c.redo_list};
+		HIPCHK(hipLaunchKernel(kf, grid, dim3((unsigned)sgh_block_threads(pl.ni, pl.rj)), args, pl.main_lds, c.s));
+		if (pl.wexp) {	/* the exported columns, before anything reads the redo list */
+			hipLaunchKernelGGL(k_hist_slow, dim3(3072), dim3(64), 0, c.s, p, redo_count, c.redo_list);	/* 12 waves per CU (153 VGPRs) */
+			HIPCHK(hipGetLastError());
+		}
+	} else if (pl.main == SG_MAIN_LINFIT) {
+		const void *kf = linfit_kernel(pl);
+		if (!kf)
+			return set_err(ctx, SG_ERR_GENERIC, "no histogram kernel for this case%s%.0ld", "", 0);
+		HIPCHK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.main_lds));
+		void *args[] = {&p, &redo_count, &c.redo_list};
+		HIPCHK(hipLaunchKernel(kf, grid, dim3(pl.main_threads), args, pl.main_lds, c.s));
+	} else if (pl.main == SG_MAIN_SORTED) {
+		HIPCHK(launch_sorted(pl.nreg, false, grid, pl.sorted_lds, c.s, p, nullptr, nullptr));
+	} else {
+		hipLaunchKernelGGL(k_list_all, grid, dim3(pl.main_threads), 0, c.s, p);
+		HIPCHK(hipGetLastError());
+	}
+	HIPCHK(hipEventRecord(cev[1], c.s));
+	return SG_OK;
+}
+
+/* the compact columns and the redo pixels of the histogram / linfit kernels, routed on the
+ * device (SgRedoRoute) */
+static int launch_redo(StackCall &c, const SgStackPlan &pl) {
+	sg_ctx *ctx = c.ctx;
+	SgStackParams &p = c.p;
+	unsigned int *redo_count = c.fl + SG_FL_REDO;
+	const dim3 lgrid(SG_LIST_GRID);
+	if (pl.compact) {
+		/* the compact columns, any count up to the capacity (grid-stride) */
+		SgStackParams q = p;
+		q.cmp_src = p.cmp_cols;
+		HIPCHK(launch_sorted(pl.nreg, true, lgrid, pl.sorted_lds, c.ts, q, p.cmp_list, p.cmp_count));
+	}
+	if (pl.redo == SG_REDO_REPLAY_THEN_SORTED) {
+		SgStackParams q = p;
+		q.list_minn = pl.list_minn;	/* idle unless the list is longer */
+		HIPCHK(launch_sorted(pl.nreg, true, lgrid, pl.sorted_lds, c.ts, q, c.redo_list, redo_count));
+		p.rp_list = c.redo_list;
+		p.rp_count = redo_count;
+		p.rp_maxn = pl.rp_maxn;
+	} else if (pl.redo == SG_REDO_SORTED) {
+		HIPCHK(launch_sorted(pl.nreg, true, lgrid, pl.sorted_lds, c.ts, p, c.redo_list, redo_count));
+	} else if (pl.redo == SG_REDO_TO_LITERAL) {
+		hipLaunchKernelGGL(k_redo_to_literal, dim3(64), dim3(256), 0, c.ts, p, (const unsigned int *)c.redo_list,
+				(const unsigned int *)redo_count, 0xFFFFFFFFu);
+		HIPCHK(hipGetLastError());
+	}
+	return SG_OK;
+}
+
+/* exact wave-per-pixel replay of queued SIGMA / WINSORIZED pixels, then the literal path for
+ * what remains: two phases, grids read the count on the device */
+static int launch_replay_literal(StackCall &c, const SgStackPlan &pl) {
+	sg_ctx *ctx = c.ctx;
+	if (pl.replay_nm) {
+		void *args[] = {&c.p};
+		HIPCHK(hipLaunchKernel((const void *)SG_REPLAY_KERNELS[pl.replay_nm > 512 ? 1 : 0], dim3(2048),
+				dim3(64 * SG_REPLAY_WAVES), args, 0, c.ts));
+	}
+	for (int phase = 1; phase <= 2; phase++) {
+		hipLaunchKernelGGL(k_stack_literal, dim3(pl.lit_threads / 64), dim3(64), 0, c.ts, c.p, c.ct, 0u,
+				(uint8_t *)c.sb->scratch.p, phase);
+		HIPCHK(hipGetLastError());
+	}
+	return SG_OK;
+}
+
+/* SUM / MEAN without rejection / MAX / MIN: the reduce kernel and SUM's scaling */
+static int launch_reduce(StackCall &c, const SgStackPlan &pl, int sum_mode, sg_stack_stats &st) {
+	sg_ctx *ctx = c.ctx;
+	SgDevice &dv = *c.dv;
+	SgStackParams &p = c.p;
+	if (pl.sum) {
+		HIPCHK(ensure(dv.sum_buf, sizeof(uint32_t) * pl.npix_img));
+		p.sum_buf = (uint32_t *)dv.sum_buf.p;
+	}
+	const dim3 grid(pl.main_grid[0], pl.main_grid[1], pl.main_grid[2]);
+	HIPCHK(hipEventRecord(dv.cev[c.slot][0], c.s));
+	if (pl.main == SG_MAIN_REDUCE3) {
+		const int g = log2_index(pl.seg, 3);
+		if (g < 0 || pl.m < 0 || pl.m > 4)
+			return set_err(ctx, SG_ERR_GENERIC, "no reduce kernel for this case%s%.0ld", "", 0);
+		void *args[] = {&p, &p.hist_tab, &p.shifty};
+		HIPCHK(hipLaunchKernel((const void *)SG_REDUCE3_KERNELS[pl.m][g], grid, dim3(pl.main_threads), args, 0, c.s));
+	} else if (pl.main == SG_MAIN_REDUCE2) {
+		hipLaunchKernelGGL(k_stack_reduce2, grid, dim3(pl.main_threads), 0, c.s, p);
+	} else {
+		hipLaunchKernelGGL(k_stack_reduce, grid, dim3(pl.main_threads), 0, c.s, p);
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(dv.cev[c.slot][1], c.s));
+	if (pl.sum && (sum_mode == SUM_WHOLE || sum_mode == SUM_LAST_BAND)) {
+		/* the 65535/max scaling (:328-342) needs the maximum over the whole image: a
+		 * streamed sequence finalises every row once its last band is summed */
+		SgStackParams pf = p;
+		dim3 gf(pl.fin_grid_x, (unsigned)pl.nrows, (unsigned)pl.C);
+		if (sum_mode == SUM_LAST_BAND) {
+			pf.row_begin = 0;
+			pf.row_end = pl.H;
+			gf.y = pl.H;
+		}
+		hipLaunchKernelGGL(k_sum_finalize, gf, dim3(256), 0, c.s, pf);
+		HIPCHK(hipGetLastError());
+		st.launches++;
+	}
+	return SG_OK;
+}
+
+/* the counters back to the host: queued; a synchronous call folds them at once, an async one
+ * when its slot is needed again or at sg_stack_collect */
+static int finalize_counters(StackCall &c, const SgStackPlan &pl, const sg_stack_stats &st) {
+	sg_ctx *ctx = c.ctx;
+	SgDevice &dv = *c.dv;
+	if (SG_DBG(c.p) == 12)
+		sg_dbg_why_dump(c.ts);
+	hipLaunchKernelGGL(k_ctr_finalize, dim3(1), dim3(256), 0, c.ts, (unsigned long long *)c.p.rej,
+			dv.ctr_hd + (size_t)c.slot * (SG_CTR_HOSTB / sizeof(unsigned long long)));
+	HIPCHK(hipGetLastError());
+	dv.ctr_clean[c.slot] = true;
+	HIPCHK(hipEventRecord(dv.cev[c.slot][2], c.ts));
+	dv.pend_sum_read[c.slot] = pl.sum;
+	dv.pstats[c.slot] = st;
+	dv.pend[c.slot] = true;
+	dv.pend_seq[c.slot] = ++dv.seq;
+	return SG_OK;
+}
+
+/* every launch of a planned call, in order */
+static int launch_stack(StackCall &c, const SgStackPlan &pl, int sum_mode, bool async, sg_stack_stats &st) {
+	if (int rc = prepare_counters(c, pl, sum_mode))
+		return rc;
+	/* the capacities of the compact and export lists; clamped to the counts when folded */
+	st.path = pl.path;
+	st.launches = pl.launches;
+	st.main_kernel_blocks = pl.main_kernel_blocks;
+	st.compact_pixels = pl.compact ? pl.cmp_cap : 0;
+	st.exported_pixels = pl.wexp ? pl.wx_cap : 0;
+	st.norm_fma = pl.norm_fma;
+	if (!pl.rejection_family) {
+		if (int rc = stage_inputs(c, pl))
+			return rc;
+		if (int rc = launch_reduce(c, pl, sum_mode, st))
+			return rc;
+		return finalize_counters(c, pl, st);
+	}
+	if (int rc = prepare_rejection_buffers(c, pl))
+		return rc;
+	if (int rc = stage_inputs(c, pl))
+		return rc;
+	if (int rc = launch_rejection_main(c, pl))
+		return rc;
+	if (int rc = to_tail(c, pl, async))
+		return rc;
+	if (pl.redo != SG_REDO_NONE)
+		if (int rc = launch_redo(c, pl))
+			return rc;
+	if (int rc = launch_replay_literal(c, pl))
+		return rc;
+	return finalize_counters(c, pl, st);
+}
+
 static int stack_device_core(sg_ctx *ctx, int dev_index, const sg_stack_desc *d,
 		const uint16_t *d_frames, int64_t frame_stride, int64_t plane_stride, uint16_t *d_out,
 		int row_begin, int row_end, uint64_t rej[3][2], uint64_t *maxim_out, void *stream, int sum_mode,
@@ -411,17 +764,10 @@ static int stack_device_core(sg_ctx *ctx, int dev_index, const sg_stack_desc *d,
 	if (!ctx || !d || dev_index < 0 || dev_index >= (int)ctx->dev.size())
 		return SG_ERR_GENERIC;
 	SgDevice &dv = ctx->dev[dev_index];
-	const int N = d->nb_frames, W = d->width, H = d->height, C = d->nb_layers;
-	if (N < 2)
-		return set_err(ctx, SG_ERR_GENERIC, "select at least two frames (%s%ld)", "", N);
-	if (W <= 0 || H <= 0 || C < 1 || C > 3 || row_begin < 0 || row_end > H || row_begin >= row_end)
-		return set_err(ctx, SG_ERR_SIZE, "bad geometry%s %ld", "", 0);
-	if (d->method < 0 || d->method > 4)
-		return set_err(ctx, SG_ERR_GENERIC, "unknown method%s %ld", "", d->method);
+	SgStackPlan pl;
+	if (int rc = sg_stack_plan_args(d, row_begin, row_end, pl))
+		return set_err(ctx, rc, "%s%.0ld", pl.err, 0);
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
-	const int nrows = row_end - row_begin;
-	const size_t npix_img = (size_t)C * H * W;
 	/* this call's statistics: the device's own record (one thread per device), published to the
 	 * context when the call returns, whatever the outcome */
 	sg_stack_stats &st = dv.stats;
@@ -437,667 +783,28 @@ static int stack_device_core(sg_ctx *ctx, int dev_index, const sg_stack_desc *d,
 			c->stats = s;
 		}
 	} publish{ctx, st, !async};
-
-	SgStackParams p;
-	memset(&p, 0, sizeof p);
-	p.frames = d_frames;
-	p.frame_stride = frame_stride;
-	p.plane_stride = plane_stride;
-	p.out = d_out;
-	p.N = N;
-	p.W = W;
-	p.H = H;
-	p.C = C;
-	p.method = d->method;
-	p.rejection = d->rejection;
-	p.normalize = (d->method == SG_STACK_MEAN || d->method == SG_STACK_MEDIAN) ? d->normalize : 0;
-	p.sig0 = d->sig[0];
-	p.sig1 = d->sig[1];
-	p.use_shift = (d->method != SG_STACK_MEDIAN) && d->shiftx && d->shifty;
-	p.row_begin = row_begin;
-	p.row_end = row_end;
-	p.res_begin = 0;
-	p.res_end = H;
-	if (d->resident_rows[0] != 0 || d->resident_rows[1] != 0) {
-		p.res_begin = d->resident_rows[0];
-		p.res_end = d->resident_rows[1];
-		if (p.res_begin < 0 || p.res_end > H || p.res_begin >= p.res_end)
-			return set_err(ctx, SG_ERR_SIZE, "bad resident row range%s %ld", "", (long)p.res_begin);
-	}
-	p.sy_min = p.sy_max = 0;
-	if (p.use_shift) {
-		p.sy_min = p.sy_max = d->shifty[0];
-		for (int i = 1; i < N; i++) {
-			p.sy_min = std::min(p.sy_min, d->shifty[i]);
-			p.sy_max = std::max(p.sy_max, d->shifty[i]);
-		}
-	}
-	{
-		/* the frame rows the band's output rows read (R - shifty, :1550-1577) must be resident */
-		const int lo = (int)std::max<int64_t>(0, (int64_t)row_begin - p.sy_max);
-		const int hi = (int)std::min<int64_t>(H - 1, (int64_t)row_end - 1 - p.sy_min);
-		if (lo <= hi && (lo < p.res_begin || hi >= p.res_end)) {
-			char m[160];
-			snprintf(m, sizeof m, "frame rows %d..%d read by the band are not all resident (%d..%d)", lo, hi,
-					p.res_begin, p.res_end - 1);
-			return set_err(ctx, SG_ERR_SIZE, "%s%.0ld", m, 0);
-		}
-	}
-	p.dbg = ctx->knobs.hist_dbg;
-	p.prio = ctx->knobs.hist_prio;	/* 1 measured best: 4.73 -> 4.58 ms (scripts/gpu_prio.sh) */
-	p.wins_cap = ctx->knobs.wins_cap;
-
-	/* per-frame constants: shifts + normalisation coefficients */
-	const int Npad = (N + 15) & ~15;	/* histogram-path table: 64-byte aligned, padded */
-	/* layout: c1[Npad] int, sx2[Npad] int16, shiftx[N], shifty[N]; the call's inputs (this
-	 * table, the normalisation coefficients, the chain tables) reach the device in one copy
-	 * (flush_inputs, right before the first kernel) */
-	std::vector<int> sh(Npad + Npad / 2 + 2 * N, 0);
-	std::vector<double> nm;
-	std::vector<int> tables, ztab;
-	/* the histogram path addresses a frame plane with 32-bit offsets: (R - sy) W 2 must fit */
-	bool hist_addr_ok = (int64_t)H * W * 2 <= (1ll << 30);
-	{
-		/* per frame c1 = shifty*W*2 + 2*shiftx and sx2 = 2*shiftx for the histogram path
-		 * (zeros when there is no registration data), then the plain shift arrays */
-		int16_t *sx2 = (int16_t *)(sh.data() + Npad);
-		p.hist_maxsx = 0;
-		for (int i = 0; p.use_shift && i < N; i++) {
-			const int64_t sy = d->shifty[i], sx = d->shiftx[i];
-			const int64_t asy = sy < 0 ? -sy : sy, asx = sx < 0 ? -sx : sx;
-			if ((int64_t)(H + asy) * W * 2 + 2 * asx >= (1ll << 31) || asx > 16383)
-				hist_addr_ok = false;
-			sh[i] = (int)(sy * W * 2 + 2 * sx);
-			sx2[i] = (int16_t)(2 * sx);
-			if (asx > p.hist_maxsx)
-				p.hist_maxsx = (int)asx;
-		}
-		if (p.use_shift) {
-			memcpy(sh.data() + Npad + Npad / 2, d->shiftx, sizeof(int) * N);
-			memcpy(sh.data() + Npad + Npad / 2 + N, d->shifty, sizeof(int) * N);
-		}
-	}
-	if (p.normalize) {
-		nm.resize(3 * N);
-		for (int i = 0; i < N; i++) {
-			nm[i] = d->offset ? d->offset[i] : 0.0;
-			nm[N + i] = d->mul ? d->mul[i] : 1.0;
-			nm[2 * N + i] = d->scale ? d->scale[i] : 1.0;
-		}
-		/* the histogram path's per-frame pair {scale, offset} (additive) or {scale, mul}
-		 * (multiplicative), read with one scalar load per frame */
-		const bool additive = p.normalize == SG_ADDITIVE || p.normalize == SG_ADDITIVE_SCALING;
-		/* + Npad single-rounding candidate pairs and the flag word of k_norm_fma_check (bit 0: no fma
-		 * load, bit 1: no integer load; the check ORs in what it finds) */
-		nm.resize(3 * N + 6 * Npad + 2, 0.0);	/* + the integer offsets of k_norm_fma_check's scale-1 form */
-		{
-			/* SG_NORM_FMA 0: neither form, 1: the fma only, 2 (default): the integer form first */
-			const unsigned int staged = ctx->knobs.norm_fma == 0 ? 3u : (ctx->knobs.norm_fma == 1 ? 2u : 0u);
-			memcpy(&nm[3 * N + 4 * Npad], &staged, sizeof staged);
-		}
-		/* additive: when every offset - 0.5 is exact (TwoSum error 0), the pair carries
-		 * offset - 0.5 and the kernel folds round_to_WORD's + 0.5 into the subtraction
-		 * (NORM 3: trunc(v scale - (offset - 0.5)), one fp64 add per sample less; equal to
-		 * trunc((v scale - offset) + 0.5) whenever the fold is exact, tests/test_norm_fold.py) */
-		bool fold = additive;
-		for (int i = 0; fold && i < N; i++) {
-			const double b = nm[i], c = b - 0.5, bb = c - b;
-			fold = ((b - (c - bb)) + (-0.5 - bb)) == 0.0;
-		}
-		p.hist_norm_fold = fold ? 1 : 0;
-		for (int i = 0; i < N; i++) {
-			nm[3 * N + 2 * i] = nm[2 * N + i];
-			nm[3 * N + 2 * i + 1] = additive ? (fold ? nm[i] - 0.5 : nm[i]) : nm[N + i];
-		}
-	}
-	/* additive normalisation with shifts: a row whose shifted source row leaves frame f holds
-	 * f's normalised zero round_to_WORD(0 scale - offset) (:1550-1577 zero fill, then
-	 * :1635-1652); the histogram path takes those values per border row from this table
-	 * (SghPix::zmax) instead of sending the rows to the redo list */
-	if (p.use_shift && (p.normalize == SG_ADDITIVE || p.normalize == SG_ADDITIVE_SCALING)) {
-		int k1 = std::max(0, p.sy_max), k2 = std::max(0, -p.sy_min);
-		if (k1 + k2 >= H) {
-			k1 = H;
-			k2 = 0;
-		}
-		ztab.assign((size_t)8 * (k1 + k2), 0);
-		bool any = false;
-		for (int t = 0; t < k1 + k2; t++) {
-			const int R = t < k1 ? t : H - k2 + (t - k1);
-			int zc = 0, zmin = 65535, zmax = 0;
-			long long zs = 0, zss = 0;	/* 64-bit: N up to 65535 normalised zeros up to 65534 */
-			for (int f = 0; f < N; f++) {
-				const int sr = R - d->shifty[f];
-				if (sr >= 0 && sr < H)
-					continue;
-				const double x = 0.0 * nm[2 * N + f] - nm[f];	/* v scale - offset at v = 0 */
-				const int z = x <= 0.0 ? 0 : (x > 65535.0 ? 65535 : (int)(x + 0.5));
-				if (z == 0 || z == 65535)
-					continue;
-				zc++;
-				zs += z;
-				zss += (long long)z * z;
-				zmin = std::min(zmin, z);
-				zmax = std::max(zmax, z);
-			}
-			if (!zc)
-				continue;
-			any = true;
-			int *e = &ztab[(size_t)8 * t];
-			e[0] = zc;
-			e[1] = (int)(uint32_t)(zs & 0xFFFFFFFFll);
-			e[6] = (int)(zs >> 32);
-			e[2] = (int)(uint32_t)(zss & 0xFFFFFFFFll);
-			e[3] = (int)(zss >> 32);
-			e[4] = zmin;
-			e[5] = zmax;
-		}
-		if (any) {
-			p.ztab_k1 = k1;
-			p.ztab_k2 = k2;
-		} else {
-			ztab.clear();
-		}
-	}
-	SgChainTables ct;
-	memset(&ct, 0, sizeof ct);
-	/* the counter slot (and its buffers): a synchronous call uses slot 0, an async call the free
-	 * slot, folding the older pending call when both are taken */
-	int slot = 0;
-	if (async) {
-		if (dv.pend[0] && dv.pend[1])
-			stack_fold_acc(ctx, dv, dv.pend_seq[0] < dv.pend_seq[1] ? 0 : 1);
-		slot = dv.pend[0] ? 1 : 0;
-	} else if (dv.pend[0]) {
-		stack_fold_acc(ctx, dv, 0);
-	}
-	SgSlot &sb = dv.sl[slot];
-	/* one pinned host block -> one device block; sets the kernels' pointers into it */
-	auto flush_inputs = [&]() -> int {
-		const size_t b_sh = sizeof(int) * sh.size(), o_nm = (b_sh + 255) & ~(size_t)255;
-		const size_t b_nm = sizeof(double) * nm.size(), o_tb = (o_nm + b_nm + 255) & ~(size_t)255;
-		const size_t o_zt = (o_tb + sizeof(int) * tables.size() + 255) & ~(size_t)255;
-		const size_t tot = (o_zt + sizeof(int) * ztab.size() + 15) & ~(size_t)15;
-		if (sb.stage_pending) {	/* an earlier call's copy may still read the host block */
-			HIPCHK(hipEventSynchronize(sb.stage_ev));
-			sb.stage_pending = false;
-		}
-		if (sb.stage_h_size < tot) {
-			if (sb.stage_h)
-				(void)hipHostFree(sb.stage_h);
-			sb.stage_h = nullptr;
-			sb.stage_h_size = 0;
-			/* coherent: the device reads it uncached, so no call sees an earlier call's inputs */
-			HIPCHK(hipHostMalloc(&sb.stage_h, tot, hipHostMallocMapped | hipHostMallocCoherent));
-			sb.stage_h_size = tot;
-			HIPCHK(hipHostGetDevicePointer(&sb.stage_d, sb.stage_h, 0));
-		}
-		HIPCHK(ensure(sb.inb, tot));
-		char *hb = (char *)sb.stage_h;
-		memcpy(hb, sh.data(), b_sh);
-		if (b_nm)
-			memcpy(hb + o_nm, nm.data(), b_nm);
-		if (!tables.empty())
-			memcpy(hb + o_tb, tables.data(), sizeof(int) * tables.size());
-		if (!ztab.empty())
-			memcpy(hb + o_zt, ztab.data(), sizeof(int) * ztab.size());
-		hipLaunchKernelGGL(k_stage_copy, dim3((unsigned)std::min<size_t>(64, (tot / 16 + 255) / 256)), dim3(256), 0, s,
-				(uint4 *)sb.inb.p, (const uint4 *)sb.stage_d, (unsigned int)(tot / 16));
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(sb.stage_ev, s));
-		sb.stage_pending = true;
-		const char *db = (const char *)sb.inb.p;
-		p.hist_tab = (const int *)db;
-		p.hist_npad = Npad;
-		if (p.use_shift) {
-			p.shiftx = p.hist_tab + Npad + Npad / 2;
-			p.shifty = p.shiftx + N;
-		}
-		if (p.normalize) {
-			p.offset = (const double *)(db + o_nm);
-			p.mul = p.offset + N;
-			p.scale = p.offset + 2 * N;
-			p.hist_norm = p.offset + 3 * N;
-		}
-		p.ztab = ztab.empty() ? nullptr : (const int *)(db + o_zt);
-		if (!tables.empty()) {
-			const int *tb = (const int *)(db + o_tb);
-			ct.blk_of_row = tb;
-			ct.blk_channel = tb + (size_t)C * H;
-			ct.blk_start = ct.blk_channel + ct.nblocks;
-			ct.blk_end = ct.blk_start + ct.nblocks;
-			ct.blk_first = ct.blk_end + ct.nblocks;
-		}
-		return SG_OK;
-	};
-	/* counters: rejection shards, then {flag count, walk fault, redo count, compact count, loop
-	 * fault} and the sum maximum 64 bytes further (kept across the bands of a streamed SUM); one
-	 * memset, one read-back.  A synchronous call uses slot 0 (a streamed SUM keeps its maximum
-	 * there); an async call the free slot, folding the older pending call when both are taken */
-	const size_t REJB = SG_CTR_REJB, CTRB = SG_CTRB;
-	{
-		const void *old_ctr = dv.ctr.p;
-		HIPCHK(ensure(dv.ctr, 2 * CTRB));
-		if (dv.ctr.p != old_ctr)
-			dv.ctr_clean[0] = dv.ctr_clean[1] = false;
-	}
-	if (!dv.ctr_h) {
-		HIPCHK(hipHostMalloc(&dv.ctr_h, 2 * SG_CTR_HOSTB, hipHostMallocMapped | hipHostMallocCoherent));
-		HIPCHK(hipHostGetDevicePointer((void **)&dv.ctr_hd, dv.ctr_h, 0));
-	}
-	char *cblk = (char *)dv.ctr.p + (size_t)slot * CTRB;
-	hipEvent_t *cev = dv.cev[slot];
-	/* the counters are zero when the slot's last call finished (k_ctr_finalize); a fresh or
-	 * failed slot is cleared here (SUM keeps its maximum across the bands of a streamed sum) */
-	const bool clear_max = sum_mode == SUM_WHOLE || sum_mode == SUM_FIRST_BAND;
-	if (!dv.ctr_clean[slot])
-		HIPCHK(hipMemsetAsync(cblk, 0, clear_max ? CTRB : REJB + 64, s));
-	else if (clear_max && d->method == SG_STACK_SUM)
-		HIPCHK(hipMemsetAsync(cblk + REJB + 64, 0, sizeof(unsigned int), s));
-	dv.ctr_clean[slot] = false;
-	p.rej = (unsigned long long *)cblk;
-	p.flag_count = (unsigned int *)(cblk + REJB);
-	p.walk_fault = p.flag_count + 1;
-	p.loop_fault = p.flag_count + 4;
-	p.maxim = (unsigned int *)(cblk + REJB + 64);
-
-	/* stack_mean_with_rejection reads a block's rows with area.y += shifty; when a block that
-	 * does not start at the top (area.y > 0) is shifted partly above the frame (area.y + shifty
-	 * < 0 <= area.y + h - 1 + shifty) it places the rows it reads at offset W (area.y - shifty)
-	 * instead of W (-area.y - shifty) (src/stacking/stacking.c:1555-1561): the rows land 2 area.y
-	 * too low and run 2 area.y + h - largest_block_h rows past its block buffer, always a heap
-	 * overflow (the neighbouring buffer or the allocator's data).  No defined result exists to
-	 * reproduce, so the call refuses the shifts instead of zero filling silently */
-	if (d->method == SG_STACK_MEAN && p.use_shift && p.sy_min < 0) {
-		const int nthr = d->max_thread > 0 ? d->max_thread : default_threads();
-		const int maxrows = d->max_number_of_rows > 0 ? d->max_number_of_rows : H;
-		std::vector<Block> blocks;
-		if (make_blocks(H, C, maxrows, nthr, blocks) == 0)
-			for (const Block &b : blocks) {
-				const long ay = b.start_row, ah = b.end_row - b.start_row + 1;
-				if (ay > 0 && ay + p.sy_min < 0 && ay + ah - 1 + p.sy_max >= 0) {
-					bool hit = false;
-					for (int i = 0; i < N && !hit; i++)
-						hit = ay + d->shifty[i] < 0 && ay + ah - 1 + d->shifty[i] >= 0;
-					if (hit) {
-						char m[320];
-						snprintf(m, sizeof m, "a registration shift of %d rows reaches above the block starting at "
-								"row %ld: the reference overflows its block buffer there (stacking.c:1555-1561); "
-								"use more rows per block (max_number_of_rows / fewer threads)", p.sy_min, ay);
-						return set_err(ctx, SG_ERR_GENERIC, "%s%.0ld", m, 0);
-					}
-				}
-			}
-	}
-	const bool sorted = (d->method == SG_STACK_MEDIAN) ||
-		(d->method == SG_STACK_MEAN && d->rejection != SG_NO_REJEC);
-	/* everything after the main kernel runs on ts: the call's stream, or the device's tail stream
-	 * for an async call whose result is wanted at sg_stack_collect only (it then overlaps the
-	 * next call's main kernel, which uses the other slot's buffers) */
-	hipStream_t ts = s;
-	auto to_tail = [&]() -> int {
-		if (!(async && (d->flags & SG_STACK_RESULT_AT_COLLECT)))
-			return SG_OK;
-		if (!dv.tail) {
-			HIPCHK(hipStreamCreateWithFlags(&dv.tail, hipStreamNonBlocking));
-			HIPCHK(hipEventCreateWithFlags(&dv.tail_ev, hipEventDisableTiming));
-			HIPCHK(hipEventCreateWithFlags(&dv.tail_done_ev, hipEventDisableTiming));
-		}
-		HIPCHK(hipEventRecord(dv.tail_ev, s));
-		HIPCHK(hipStreamWaitEvent(dv.tail, dv.tail_ev, 0));
-		ts = dv.tail;
-		return SG_OK;
-	};
-	if (sorted) {
-		const int nreg = pick_nreg(N);
-		/* histogram fast path (sg_stack_hist.hip): SIGMA / WINSORIZED / PERCENTILE rejection and
-		 * stack_median, any normalisation, 16 <= N <= 65535 (per-lane zero / 65535 counters are
-		 * 16-bit halves) */
-		/* LINEARFIT's decision-exact kernel (k_stack_linfit, sg_stack.hip) takes the histogram
-		 * path's place: its redo list goes to the sorted kernel's exact replay the same way */
-		const bool linfit_fast = d->kernel_path != SG_PATH_SORTED && d->method == SG_STACK_MEAN &&
-			d->rejection == SG_LINEARFIT && N >= 16 && N <= 1024 && ctx->knobs.linfit_fast;
-		const bool hist = linfit_fast || (d->kernel_path != SG_PATH_SORTED && N >= 16 && N <= 65535 && hist_addr_ok &&
-			(d->method == SG_STACK_MEDIAN || (d->method == SG_STACK_MEAN && (d->rejection == SG_SIGMA ||
-					d->rejection == SG_WINSORIZED || d->rejection == SG_PERCENTILE ||
-					(d->rejection == SG_SIGMEDIAN && ctx->knobs.hist_sigmedian)))));
-		/* beyond the sorted kernel's 1024 frames only the histogram path runs; its redo pixels
-		 * all go to the replay / literal kernels (they take any N) */
-		/* beyond the sorted kernel's 1024 frames a stack without a histogram path (LINEARFIT, or
-		 * planes past the histogram's 32-bit offsets) goes to the literal kernel pixel by pixel: slow,
-		 * but any N as the reference (:1486-1507) */
-		const bool literal_all = !nreg && !hist;
-		const size_t npix_launch = (size_t)C * nrows * W;
-		HIPCHK(ensure(sb.flag_list, sizeof(unsigned int) * npix_launch));
-		{
-			/* pixel classes carry this call's epoch (sg_flag_get): no per-call clear; the map is
-			 * cleared when it is new or the 31 epochs wrap */
-			const void *old_map = sb.flag_map.p;
-			HIPCHK(ensure(sb.flag_map, npix_img));
-			if (sb.flag_map.p != old_map || sb.flag_epoch <= 0 || sb.flag_epoch >= 31) {
-				HIPCHK(hipMemsetAsync(sb.flag_map.p, 0, sb.flag_map.size, s));
-				sb.flag_epoch = 0;
-			}
-			p.flag_epoch = (unsigned int)++sb.flag_epoch;
-		}
-		p.flag_list = (unsigned int *)sb.flag_list.p;
-		p.flag_cap = (unsigned int)npix_launch;
-		p.flag_map = (uint8_t *)sb.flag_map.p;
-
-		/* reference thread order tables for the stale-state chains */
-		int nthr = d->max_thread > 0 ? d->max_thread : default_threads();
-		int maxrows = d->max_number_of_rows > 0 ? d->max_number_of_rows : H;
-		std::vector<Block> blocks;
-		if (make_blocks(H, C, maxrows, nthr, blocks))
-			return set_err(ctx, SG_ERR_GENERIC, "block partition failed (the reference would read "
-					"uninitialised blocks)%s%ld", "", 0);
-		const int nb = (int)blocks.size();
-		tables.assign((size_t)C * H + 4 * nb, 0);
-		int *blk_of_row = tables.data(), *bch = blk_of_row + (size_t)C * H, *bst = bch + nb,
-		    *ben = bst + nb, *bfi = ben + nb;
-		for (int b = 0; b < nb; b++) {
-			bch[b] = (int)blocks[b].channel;
-			bst[b] = (int)blocks[b].start_row;
-			ben[b] = (int)blocks[b].end_row;
-			for (long r = blocks[b].start_row; r <= blocks[b].end_row; r++)
-				blk_of_row[(size_t)blocks[b].channel * H + r] = b;
-		}
-		for (int t = 0; t < nthr; t++) {
-			long b0, b1;
-			omp_static_chunk(nb, nthr, t, &b0, &b1);
-			for (long b = b0; b < b1; b++)
-				bfi[b] = (int)b0;
-		}
-		ct.nblocks = nb;
-		if (int rc = flush_inputs())
-			return rc;
-
-		if (d->method == SG_STACK_MEAN && p.rejection == SG_LINEARFIT) {
-			HIPCHK(ensure(sb.lin_tab, sizeof(double) * 2 * ((size_t)N + 1)));
-			hipLaunchKernelGGL(k_linfit_tables, dim3((N + 64) / 64), dim3(64), 0, s, (double *)sb.lin_tab.p, N);
-			HIPCHK(hipGetLastError());
-			p.linfit_tab = (const double *)sb.lin_tab.p;
-		}
-		const int ntx = (W + SG_TILE_W - 1) / SG_TILE_W;
-		const size_t nblk = (size_t)ntx * nrows * C;
-		/* LINEARFIT: + one rejected[] bit per frame and pixel of the tile (reject_linearfit) */
-		const size_t lds = (size_t)N * SG_STAGE_STRIDE * 2 +
-			(d->rejection == SG_LINEARFIT ? (size_t)64 * ((N + 31) / 32) * 4 : 0);
-		if (hist) {
-			HIPCHK(ensure(sb.redo, sizeof(unsigned int) * (npix_launch + 16)));
-			unsigned int *redo_count = p.flag_count + 2;	/* cleared with the counters */
-			unsigned int *redo_list = (unsigned int *)sb.redo.p + 16;
-			HIPCHK(hipEventRecord(cev[0], s));
-			/* NORM: 0 none, 1 additive (round(v scale - offset)), 2 multiplicative (round(v scale mul)),
-			 * 3 additive with the folded + 0.5 */
-			const int norm = p.normalize == SG_NO_NORM ? 0 :
-				(p.normalize == SG_ADDITIVE || p.normalize == SG_ADDITIVE_SCALING) ? (p.hist_norm_fold ? 3 : 1) : 2;
-			/* tile = 128 NI pixels of a row, 4 NI waves: NI = 1 by default (sg_stack_hist.hip);
-			 * the A/B NI = 2 (SG_HIST_NI=2) exists without normalisation only (it spills there:
-			 * the per-sample double arithmetic of two pixel pairs) */
-			const int ni = (norm == 0 && ctx->knobs.hist_ni == 2 && (d->method == SG_STACK_MEAN &&
-						(p.rejection == SG_SIGMA || p.rejection == SG_WINSORIZED))) ? 2 : 1;
-			const size_t nblk_h = (size_t)((W + 128 * ni - 1) / (128 * ni)) * nrows * C;
-			if (SG_DBG(p) == 14) {	/* A/B: report the resident workgroups per CU */
-				int per_cu = -1;
-				(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ni == 2 ? (const void *)k_stack_hist<2, 0, 2>
-						: (const void *)k_stack_hist<2, 0, 1>, sgh_block_threads(ni, 2), (size_t)ctx->knobs.hist_ldspad);
-				hipDeviceProp_t prop;
-				(void)hipGetDeviceProperties(&prop, dv.id);
-				fprintf(stderr, "k_stack_hist: %d workgroups/CU (lds/CU %zu, lds/block max %zu, pad %d)\n", per_cu,
-						(size_t)prop.maxSharedMemoryPerMultiProcessor, (size_t)prop.sharedMemPerBlock, ctx->knobs.hist_ldspad);
-			}
-			const size_t lds_pad = (size_t)ctx->knobs.hist_ldspad;
-			/* REJ: 2 SIGMA, 4 WINSORIZED, 1 PERCENTILE, 3 SIGMEDIAN, 8 stack_median */
-			const int rj = d->method == SG_STACK_MEDIAN ? 8 : p.rejection == SG_WINSORIZED ? 4 :
-				p.rejection == SG_PERCENTILE ? 1 : p.rejection == SG_SIGMEDIAN ? 3 : 2;
-			/* normalised SIGMA / WINSORIZED: redo pixels whose samples the tile fully knows leave
-			 * their sorted columns for the sorted kernel (sgh_compact), up to a 384 MiB buffer */
-			const bool compact = !linfit_fast && norm != 0 && (rj == 2 || rj == 4) && nreg && ctx->knobs.hist_compact;
-			if (compact) {
-				const size_t cap = std::min<size_t>(npix_launch, ctx->knobs.hist_compact >= 2 ?
-						(size_t)ctx->knobs.hist_compact : ((size_t)384 << 20) / ((size_t)N * 2));
-				HIPCHK(ensure(sb.cmp_cols, cap * (size_t)N * 2));
-				HIPCHK(ensure(sb.cmp_list, cap * sizeof(unsigned int)));
-				p.cmp_cols = (uint16_t *)sb.cmp_cols.p;
-				p.cmp_list = (unsigned int *)sb.cmp_list.p;
-				p.cmp_count = p.flag_count + 3;	/* cleared with the counters */
-				p.cmp_cap = (unsigned int)cap;
-			}
-			/* WINSORIZED without normalisation: the slow columns (a zero or a 65535 sample) leave their
-			 * tiles for k_hist_slow (SG_WINS_EXPORT), up to a quarter of the launch's pixels */
-			const bool wexp = rj == 4 && norm == 0 && ni == 1 && !linfit_fast && ctx->knobs.wins_export;
-			if (wexp) {
-				const size_t cap = ((npix_launch / 4 + 63) / 64) * 64;
-				HIPCHK(ensure(sb.wx, cap * (SG_HIST_HROWS + 3) * sizeof(uint32_t)));
-				p.wx = (uint32_t *)sb.wx.p;
-				p.wx_cap = (unsigned int)cap;
-				p.wx_count = p.flag_count + 6;	/* cleared with the counters */
-				p.wx_kmax = ctx->knobs.wins_export;
-				st.exported_pixels = cap;	/* the capacity; clamped to the count when folded */
-			}
-			const dim3 hg((unsigned)nblk_h), hb((unsigned)sgh_block_threads(ni, rj));
-			/* normalised: check the single-rounding load against the reference's operations over every
-			 * u16 value of every frame (k_norm_fma_check, ~10 us); the kernel reads the verdict */
-			if (norm != 0 && !linfit_fast) {
-				if (ctx->knobs.norm_fma) {
-					hipLaunchKernelGGL(k_norm_fma_check, dim3(16, (unsigned)N), dim3(256), 0, s, (double *)p.hist_norm, N, Npad,
-							norm, p.flag_count + 7);
-					HIPCHK(hipGetLastError());
-					/* the best load allowed; the verdict replaces it when the call is folded */
-					st.norm_fma = norm != 2 && ctx->knobs.norm_fma == 2 ? 2 : 1;
-				}
-			}
-			if (linfit_fast) {
-				/* one workgroup per 64 pixels of a row, the tile's columns in LDS */
-				const int km = N <= 512 ? 8 : 16;
-				const size_t lfx_lds = (size_t)64 * (64 * km + 2) * sizeof(uint16_t);
-				/* waves per tile: 4, 8 or (KM = 8 only: 187 VGPRs at KM = 16) 16 */
-				const int lw = ctx->knobs.linfit_waves;
-				const int nw = lw == 4 ? 4 : (lw == 16 && km == 8) ? 16 : 8;
-				/* SG_LINFIT_PAIR: both pixels of a sorted pair in lockstep (lfx_pixel2_m), 4 or 8 waves */
-				const bool pr = ctx->knobs.linfit_pair && nw != 16;
-				const void *kf = pr ? (km == 8 ? (nw == 4 ? (const void *)k_stack_linfit<8, 4, true> :
-								(const void *)k_stack_linfit<8, 8, true>) :
-							(nw == 4 ? (const void *)k_stack_linfit<16, 4, true> :
-								(const void *)k_stack_linfit<16, 8, true>)) :
-					km == 8 ? (nw == 4 ? (const void *)k_stack_linfit<8, 4, false> :
-						nw == 8 ? (const void *)k_stack_linfit<8, 8, false> : (const void *)k_stack_linfit<8, 16, false>) :
-					(nw == 4 ? (const void *)k_stack_linfit<16, 4, false> : (const void *)k_stack_linfit<16, 8, false>);
-				HIPCHK(hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lfx_lds));
-				const dim3 lg((unsigned)((size_t)((W + 63) / 64) * nrows * C));
-				void *lfx_args[] = {&p, &redo_count, &redo_list};
-				HIPCHK(hipLaunchKernel(kf, lg, dim3(64 * nw), lfx_args, lfx_lds, s));
-			} else
-			switch ((rj == 4 ? 10 : rj == 1 ? 20 : rj == 8 ? 30 : rj == 3 ? 40 : 0) + norm +
-					100 * (rj == 1 || rj == 8 || rj == 3 ? 1 : ni)) {
-			case 100: hipLaunchKernelGGL((k_stack_hist<2, 0, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 101: hipLaunchKernelGGL((k_stack_hist<2, 1, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 102: hipLaunchKernelGGL((k_stack_hist<2, 2, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 103: hipLaunchKernelGGL((k_stack_hist<2, 3, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 110: hipLaunchKernelGGL((k_stack_hist<4, 0, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 111: hipLaunchKernelGGL((k_stack_hist<4, 1, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 112: hipLaunchKernelGGL((k_stack_hist<4, 2, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 113: hipLaunchKernelGGL((k_stack_hist<4, 3, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 120: hipLaunchKernelGGL((k_stack_hist<1, 0, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 121: hipLaunchKernelGGL((k_stack_hist<1, 1, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 122: hipLaunchKernelGGL((k_stack_hist<1, 2, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 123: hipLaunchKernelGGL((k_stack_hist<1, 3, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 130: hipLaunchKernelGGL((k_stack_hist<8, 0, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 131: hipLaunchKernelGGL((k_stack_hist<8, 1, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 132: hipLaunchKernelGGL((k_stack_hist<8, 2, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 133: hipLaunchKernelGGL((k_stack_hist<8, 3, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 140: hipLaunchKernelGGL((k_stack_hist<3, 0, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 141: hipLaunchKernelGGL((k_stack_hist<3, 1, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 142: hipLaunchKernelGGL((k_stack_hist<3, 2, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 143: hipLaunchKernelGGL((k_stack_hist<3, 3, 1>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 200: hipLaunchKernelGGL((k_stack_hist<2, 0, 2>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			case 210: hipLaunchKernelGGL((k_stack_hist<4, 0, 2>), hg, hb, lds_pad, s, p, p.hist_tab, (const int4 *)p.hist_norm, redo_count, redo_list); break;
-			default: return set_err(ctx, SG_ERR_GENERIC, "no histogram kernel for this case%s%.0ld", "", 0);
-			}
-			HIPCHK(hipGetLastError());
-			if (wexp) {	/* the exported columns, before anything reads the redo list */
-				hipLaunchKernelGGL(k_hist_slow, dim3(3072), dim3(64), 0, s, p, redo_count, redo_list);	/* 12 waves per CU (153 VGPRs) */
-				HIPCHK(hipGetLastError());
-			}
-			HIPCHK(hipEventRecord(cev[1], s));
-			if (int rc = to_tail())
-				return rc;
-			st.path = 1;
-			st.main_kernel_blocks = (int)nblk;
-			st.launches = 1;
-			st.compact_pixels = compact ? p.cmp_cap : 0;	/* the capacity; clamped to the count when folded */
-			const dim3 lgrid(SG_LIST_GRID);
-			if (compact) {
-				/* the compact columns, any count up to the capacity (grid-stride) */
-				SgStackParams q = p;
-				q.cmp_src = p.cmp_cols;
-				HIPCHK(launch_sorted(nreg, true, lgrid, lds, ts, q, p.cmp_list, p.cmp_count));
-				st.launches++;
-			}
-			/* the redo pixels, routed on the device (no host round trip in the call):
-			 * - SIGMA / WINSORIZED, N <= SG_REPLAY_MAXN: up to SG_REDO_REPLAY_MAX pixels straight to
-			 *   the wave-per-pixel replay (every sample of a pixel gathered by one wave at once), a
-			 *   longer list (rare: e.g. normalised zeros of rows near the frame border) through the
-			 *   sorted kernel (measured: 22 k pixels faster in the replay, 113 k slower);
-			 * - stack_median / PERCENTILE: the sorted kernel (the literal kernel's one thread per
-			 *   pixel sorts slowly: 740 pixels took 8 ms);
-			 * - N > 1024 (no sorted kernel): every redo pixel to the replay / literal kernels */
-			const bool replay_route = nreg && d->method == SG_STACK_MEAN && (p.rejection == SG_SIGMA ||
-					p.rejection == SG_WINSORIZED) && N <= SG_REPLAY_MAXN && ctx->knobs.redo_replay;
-			if (replay_route) {
-				SgStackParams q = p;
-				q.list_minn = SG_REDO_REPLAY_MAX;	/* idle unless the list is longer */
-				HIPCHK(launch_sorted(nreg, true, lgrid, lds, ts, q, redo_list, redo_count));
-				p.rp_list = redo_list;
-				p.rp_count = redo_count;
-				p.rp_maxn = SG_REDO_REPLAY_MAX;
-				st.launches++;
-			} else if (nreg) {
-				HIPCHK(launch_sorted(nreg, true, lgrid, lds, ts, p, redo_list, redo_count));
-				st.launches++;
-			} else {
-				hipLaunchKernelGGL(k_redo_to_literal, dim3(64), dim3(256), 0, ts, p, (const unsigned int *)redo_list,
-						(const unsigned int *)redo_count, 0xFFFFFFFFu);
-				HIPCHK(hipGetLastError());
-				st.launches++;
-			}
-		} else if (literal_all) {
-			HIPCHK(hipEventRecord(cev[0], s));
-			hipLaunchKernelGGL(k_list_all, dim3(1024), dim3(256), 0, s, p);
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipEventRecord(cev[1], s));
-			if (int rc = to_tail())
-				return rc;
-			st.launches = 1;
-		} else {
-			HIPCHK(hipEventRecord(cev[0], s));
-			HIPCHK(launch_sorted(nreg, false, dim3((unsigned)nblk), lds, s, p, nullptr, nullptr));
-			HIPCHK(hipEventRecord(cev[1], s));
-			if (int rc = to_tail())
-				return rc;
-			st.main_kernel_blocks = (int)nblk;
-			st.launches = 1;
-		}
-		/* exact wave-per-pixel replay of queued SIGMA / WINSORIZED pixels (the replay route's redo
-		 * list, early breaks with this pixel's own stale rejected[]), then the literal path for what
-		 * remains: two phases, grids read the count on the device */
-		const unsigned lit_threads = lit_thread_count(N);
-		HIPCHK(ensure(sb.scratch, lit_scratch_bytes(N)));
-		if (d->method == SG_STACK_MEAN && (p.rejection == SG_SIGMA || p.rejection == SG_WINSORIZED) &&
-				N <= SG_REPLAY_MAXN) {
-			if (N <= 512)	/* the per-wave LDS sized for 512 frames (k_stack_replay<SG_REPLAY_FASTN>) */
-				hipLaunchKernelGGL(k_stack_replay<512>, dim3(2048), dim3(64 * SG_REPLAY_WAVES), 0, ts, p);
-			else
-				hipLaunchKernelGGL(k_stack_replay<SG_REPLAY_MAXN>, dim3(2048), dim3(64 * SG_REPLAY_WAVES), 0, ts, p);
-			HIPCHK(hipGetLastError());
-			st.launches++;
-		}
-		for (int phase = 1; phase <= 2; phase++) {
-			hipLaunchKernelGGL(k_stack_literal, dim3(lit_threads / 64), dim3(64), 0, ts, p, ct,
-					0u, (uint8_t *)sb.scratch.p, phase);
-			HIPCHK(hipGetLastError());
-		}
-		st.launches += 2;
-	} else {
-		if (int rc = flush_inputs())
-			return rc;
-		if (d->method == SG_STACK_SUM) {
-			HIPCHK(ensure(dv.sum_buf, sizeof(uint32_t) * npix_img));
-			p.sum_buf = (uint32_t *)dv.sum_buf.p;
-		}
-		dim3 grid((W + 255) / 256, nrows, C);
-		/* pixel pairs per lane (dword loads) unless a plane is too large for a 31-bit offset */
-		const bool pairs = W >= 2 && (uint64_t)W * (uint64_t)H * 2u < (1ull << 31) && ctx->knobs.reduce1 != 1;
-		const dim3 grid2(((W + 1) / 2 + 255) / 256, nrows, C);
-		/* XCD-aware SGPR-offset loads (k_stack_reduce3) when the shifted row offsets fit 32 bits,
-		 * the per-lane pair kernel (SG_REDUCE1=2, A/B) otherwise */
-		const bool r3 = pairs && hist_addr_ok && ctx->knobs.reduce1 == 0;
-		/* 256-byte segments per wave: SEG = 1 by default (SG_REDUCE_SEG: 1 / 2 / 4, A/B; 2 and 4
-		 * measured slower, profiles/r05g_reduce_seg_*) */
-		const int seg = ctx->knobs.reduce_seg;
-		const unsigned nb3 = (unsigned)(((W + 512 * seg - 1) / (512 * seg)) * (size_t)nrows * C);
-		HIPCHK(hipEventRecord(cev[0], s));
-		if (r3) {
-			/* MEAN: the normalising instance's fp64 path costs registers: its own kernel */
-			const int m = d->method == SG_STACK_SUM ? 0 : d->method == SG_STACK_MEAN ? (p.normalize ? 2 : 1) :
-				d->method == SG_STACK_MAX ? 3 : 4;
-			switch (m * 8 + seg) {
-#define SG_R3L(M, G)                                                                            \
-			case M * 8 + G:                                                                 \
-				hipLaunchKernelGGL((k_stack_reduce3<M, G>), dim3(nb3), dim3(256), 0, s, p, p.hist_tab, p.shifty); \
-				break;
-			SG_R3L(0, 1) SG_R3L(0, 2) SG_R3L(0, 4)
-			SG_R3L(1, 1) SG_R3L(1, 2) SG_R3L(1, 4)
-			SG_R3L(2, 1) SG_R3L(2, 2) SG_R3L(2, 4)
-			SG_R3L(3, 1) SG_R3L(3, 2) SG_R3L(3, 4)
-			SG_R3L(4, 1) SG_R3L(4, 2) SG_R3L(4, 4)
-#undef SG_R3L
-			default:
-				return set_err(ctx, SG_ERR_GENERIC, "no reduce kernel for this case%s%.0ld", "", 0);
-			}
-		} else if (pairs) {
-			hipLaunchKernelGGL(k_stack_reduce2, grid2, dim3(256), 0, s, p);
-		} else {
-			hipLaunchKernelGGL(k_stack_reduce, grid, dim3(256), 0, s, p);
-		}
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(cev[1], s));
-		st.main_kernel_blocks = r3 ? (int)nb3 : pairs ? (int)(grid2.x * grid2.y * grid2.z) : (int)(grid.x * grid.y * grid.z);
-		st.launches = 1;
-		if (d->method == SG_STACK_SUM && (sum_mode == SUM_WHOLE || sum_mode == SUM_LAST_BAND)) {
-			/* the 65535/max scaling (:328-342) needs the maximum over the whole image: a
-			 * streamed sequence finalises every row once its last band is summed */
-			SgStackParams pf = p;
-			dim3 gf = grid;
-			if (sum_mode == SUM_LAST_BAND) {
-				pf.row_begin = 0;
-				pf.row_end = H;
-				gf.y = H;
-			}
-			hipLaunchKernelGGL(k_sum_finalize, gf, dim3(256), 0, s, pf);
-			HIPCHK(hipGetLastError());
-			st.launches++;
-		}
-	}
-	if (SG_DBG(p) == 12)
-		sg_dbg_why_dump(ts);
-	/* the counters back to the host: queued; a synchronous call folds them at once, an async one
-	 * when its slot is needed again or at sg_stack_collect */
-	hipLaunchKernelGGL(k_ctr_finalize, dim3(1), dim3(256), 0, ts, (unsigned long long *)cblk,
-			dv.ctr_hd + (size_t)slot * (SG_CTR_HOSTB / sizeof(unsigned long long)));
-	HIPCHK(hipGetLastError());
-	dv.ctr_clean[slot] = true;
-	HIPCHK(hipEventRecord(cev[2], ts));
-	dv.pend_sum_read[slot] = d->method == SG_STACK_SUM;
-	dv.pstats[slot] = st;
-	dv.pend[slot] = true;
-	dv.pend_seq[slot] = ++dv.seq;
+	/* an error found by the plan is returned before any device work of the call */
+	if (int rc = sg_stack_plan(d, row_begin, row_end, ctx->knobs, pl))
+		return set_err(ctx, rc, "%s%.0ld", pl.err, 0);
+	StackCall c;
+	c.ctx = ctx;
+	c.dv = &dv;
+	c.slot = choose_slot(ctx, dv, async);
+	c.sb = &dv.sl[c.slot];
+	c.s = c.ts = stream ? (hipStream_t)stream : dv.stream;
+	c.fl = c.redo_list = nullptr;
+	sg_plan_params(pl, c.p);
+	c.p.frames = d_frames;
+	c.p.frame_stride = frame_stride;
+	c.p.plane_stride = plane_stride;
+	c.p.out = d_out;
+	if (int rc = launch_stack(c, pl, sum_mode, async, st))
+		return rc;
 	if (slot_out)
-		*slot_out = slot;
+		*slot_out = c.slot;
 	if (async)
 		return SG_OK;
-	return stack_fold(ctx, dv, slot, rej, maxim_out, true);
+	return stack_fold(ctx, dv, c.slot, rej, maxim_out, true);
 }
 
 extern "C" int sg_stack_u16_device(sg_ctx *ctx, int dev_index, const sg_stack_desc *d,
@@ -1324,6 +1031,42 @@ static int pull_band(sg_ctx *ctx, SgDevice &dv, PullCall &pc, int nreaders, uint
  * theirs (:1513-1591).  The output rows stay in the device's dv.out (SUM of several devices:
  * raw sums, scaled once the maximum over every device is known).
  */
+/* output rows per band (in: the rows wanted) and frame buffers under the device's budget */
+static int pull_band_rows(sg_ctx *ctx, const sg_stack_desc *d, size_t budget, size_t row_bytes, int64_t halo,
+		int &band, int &nbuf) {
+	nbuf = 1;
+	if ((size_t)band * row_bytes <= budget)
+		return SG_OK;
+	const int64_t fit = (int64_t)(budget / row_bytes) - halo;
+	if (fit < 1)
+		return set_err(ctx, SG_ERR_SIZE, "the sequence does not fit the device even one row at a "
+				"time%s%.0ld", "", 0);
+	band = (int)std::min<int64_t>(fit, band);
+	/* several bands: two half-size buffers when a band of each still fits */
+	const int64_t fit2 = (int64_t)(budget / 2 / row_bytes) - halo;
+	if (d->method != SG_STACK_SUM && fit2 >= 1 && ctx->knobs.pull_overlap) {
+		band = (int)std::min<int64_t>(fit2, band);
+		nbuf = 2;
+	}
+	return SG_OK;
+}
+
+/* give up the band in flight (an error ends the call): wait for it, free its slot */
+static void drain_pending(SgDevice &dv, int &slot) {
+	if (slot < 0)
+		return;
+	(void)hipEventSynchronize(dv.cev[slot][2]);
+	dv.pend[slot] = false;
+	slot = -1;
+}
+
+static void add_rej(uint64_t rej[3][2], const uint64_t band[3][2]) {
+	for (int c = 0; c < 3; c++) {
+		rej[c][0] += band[c][0];
+		rej[c][1] += band[c][1];
+	}
+}
+
 static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nreaders, uint64_t rej[3][2],
 		uint64_t *maxim) {
 	SgDevice &dv = ctx->dev[(size_t)g];
@@ -1332,21 +1075,9 @@ static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nread
 	HIPCHK(hipSetDevice(dv.id));
 	const int64_t halo = std::min<int64_t>((int64_t)pc.sy_max - pc.sy_min, H);
 	const size_t row_bytes = (size_t)N * C * W * sizeof(uint16_t);	/* one row of every frame */
-	const size_t budget = host_budget(ctx, dv, N, W, H, C);
 	int band = E - B, nbuf = 1;
-	if ((size_t)band * row_bytes > budget) {
-		const int64_t fit = (int64_t)(budget / row_bytes) - halo;
-		if (fit < 1)
-			return set_err(ctx, SG_ERR_SIZE, "the sequence does not fit the device even one row at a "
-					"time%s%.0ld", "", 0);
-		band = (int)std::min<int64_t>(fit, band);
-		/* several bands: two half-size buffers when a band of each still fits */
-		const int64_t fit2 = (int64_t)(budget / 2 / row_bytes) - halo;
-		if (d->method != SG_STACK_SUM && fit2 >= 1 && ctx->knobs.pull_overlap) {
-			band = (int)std::min<int64_t>(fit2, band);
-			nbuf = 2;
-		}
-	}
+	if (int rc = pull_band_rows(ctx, d, host_budget(ctx, dv, N, W, H, C), row_bytes, halo, band, nbuf))
+		return rc;
 	const int64_t rows_cap = std::min<int64_t>(band + halo, H);
 	const size_t buf_elems = (size_t)rows_cap * W * C * N;
 	HIPCHK(ensure(dv.frames, nbuf * buf_elems * sizeof(uint16_t)));
@@ -1384,18 +1115,8 @@ static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nread
 		}
 		if (rc)
 			return rc == SG_ERR_WALK ? SG_ERR_GENERIC : rc;
-		for (int c = 0; c < 3; c++) {
-			rej[c][0] += brej[c][0];
-			rej[c][1] += brej[c][1];
-		}
+		add_rej(rej, brej);
 		return SG_OK;
-	};
-	auto drain = [&]() {
-		if (pend.slot >= 0) {
-			(void)hipEventSynchronize(dv.cev[pend.slot][2]);
-			dv.pend[pend.slot] = false;
-			pend.slot = -1;
-		}
 	};
 	int buf = 0;
 	for (int b = B; b < E;) {
@@ -1408,7 +1129,7 @@ static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nread
 		const size_t bplane = (size_t)nres * W;
 		uint16_t *fb = (uint16_t *)dv.frames.p + (size_t)buf * buf_elems;
 		if (int rc = pull_band(ctx, dv, pc, nreaders, fb, lo, nres)) {
-			drain();
+			drain_pending(dv, pend.slot);
 			return rc;
 		}
 		if (pend.slot >= 0) {	/* the previous band stacked while this one was read */
@@ -1432,7 +1153,7 @@ static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nread
 			int slot = -1;
 			if (int rc = stack_device_core(ctx, g, &bd, base, (int64_t)bplane * C, (int64_t)bplane,
 					(uint16_t *)dv.out.p, b, e, nullptr, nullptr, dv.stream, sum_mode, true, &slot)) {
-				drain();
+				drain_pending(dv, pend.slot);
 				return rc == SG_ERR_WALK ? SG_ERR_GENERIC : rc;
 			}
 			pend = {slot, b, e, hi};
@@ -1454,10 +1175,7 @@ static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nread
 		}
 		if (rc)
 			return rc == SG_ERR_WALK ? SG_ERR_GENERIC : rc;
-		for (int c = 0; c < 3; c++) {
-			rej[c][0] += brej[c][0];
-			rej[c][1] += brej[c][1];
-		}
+		add_rej(rej, brej);
 		b = e;
 	}
 	return SG_OK;
@@ -1477,13 +1195,34 @@ static int sum_finalize_rows(sg_ctx *ctx, int g, int W, int H, int C, int B, int
 	p.sum_buf = (uint32_t *)dv.sum_buf.p;
 	p.row_begin = B;
 	p.row_end = E;
-	p.maxim = (unsigned int *)((char *)dv.ctr.p + SG_CTR_REJB + 64);
+	p.maxim = flag_words(dv.ctr.p) + SG_FL_SUM_MAX;
 	HIPCHK(hipMemcpyAsync(p.maxim, &gmax, sizeof gmax, hipMemcpyHostToDevice, dv.stream));
 	hipLaunchKernelGGL(k_sum_finalize, dim3((unsigned)((W + 255) / 256), (unsigned)(E - B), (unsigned)C), dim3(256), 0,
 			dv.stream, p);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(dv.stream));
 	return SG_OK;
+}
+
+/* a host-pull call's statistics over every device */
+static void publish_multi_stats(sg_ctx *ctx, int G) {
+	sg_stack_stats agg;
+	memset(&agg, 0, sizeof agg);
+	for (int g = 0; g < G; g++) {
+		const sg_stack_stats &s = ctx->dev[(size_t)g].stats;
+		agg.kernel_ms = std::max(agg.kernel_ms, s.kernel_ms);
+		agg.total_ms = std::max(agg.total_ms, s.total_ms);
+		agg.slow_pixels += s.slow_pixels;
+		agg.chain_pixels += s.chain_pixels;
+		agg.compact_pixels += s.compact_pixels;
+		agg.exported_pixels += s.exported_pixels;
+		agg.norm_fma = std::max(agg.norm_fma, s.norm_fma);
+		agg.launches += s.launches;
+		agg.main_kernel_blocks += s.main_kernel_blocks;
+		agg.path = s.path;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	ctx->stats = agg;
 }
 
 /*
@@ -1510,12 +1249,7 @@ extern "C" int sg_stack_u16(sg_ctx *ctx, const sg_stack_desc *d, sg_read_region_
 	pc.cont = cont;
 	pc.cont_user = cont_user;
 	/* frame rows a band reads: [b - sy_max, e - 1 - sy_min] */
-	const bool use_shift = d->method != SG_STACK_MEDIAN && d->shiftx && d->shifty;
-	pc.sy_min = pc.sy_max = 0;
-	for (int i = 0; use_shift && i < N; i++) {
-		pc.sy_min = i ? std::min(pc.sy_min, d->shifty[i]) : d->shifty[i];
-		pc.sy_max = i ? std::max(pc.sy_max, d->shifty[i]) : d->shifty[i];
-	}
+	(void)sg_plan_shift_range(d, &pc.sy_min, &pc.sy_max);
 	const int G = (int)std::min<size_t>(ctx->dev.size(), (size_t)H);
 	pc.multi = G > 1;
 	/* readers per device: the reference's team size (com.max_thread) shared between the
@@ -1606,25 +1340,8 @@ extern "C" int sg_stack_u16(sg_ctx *ctx, const sg_stack_desc *d, sg_read_region_
 		}
 	if (maxim)
 		*maxim = gmax;
-	if (pc.multi) {	/* the call's statistics over every device */
-		sg_stack_stats agg;
-		memset(&agg, 0, sizeof agg);
-		for (int g = 0; g < G; g++) {
-			const sg_stack_stats &s = ctx->dev[(size_t)g].stats;
-			agg.kernel_ms = std::max(agg.kernel_ms, s.kernel_ms);
-			agg.total_ms = std::max(agg.total_ms, s.total_ms);
-			agg.slow_pixels += s.slow_pixels;
-			agg.chain_pixels += s.chain_pixels;
-			agg.compact_pixels += s.compact_pixels;
-			agg.exported_pixels += s.exported_pixels;
-			agg.norm_fma = std::max(agg.norm_fma, s.norm_fma);
-			agg.launches += s.launches;
-			agg.main_kernel_blocks += s.main_kernel_blocks;
-			agg.path = s.path;
-		}
-		std::lock_guard<std::mutex> lk(ctx->mu);
-		ctx->stats = agg;
-	}
+	if (pc.multi)
+		publish_multi_stats(ctx, G);
 	return SG_OK;
 }
 

@@ -709,3 +709,43 @@ def test_wins_export_matches_oracle(N, H, W, M):
     assert st.exported_pixels <= (H * W // 4 + 63) // 64 * 64
     assert_same(out_x, ref, f"exported N={N}")
     assert np.array_equal(rej_x, rej_ref), (rej_x, rej_ref)
+
+
+HIST_NORMS = ["none", "additive-exact", "additive-tiny", "multiplicative"]
+
+
+@pytest.mark.parametrize("norm", HIST_NORMS)
+@pytest.mark.parametrize("rejection", [sg.PERCENTILE, sg.SIGMA, sg.SIGMEDIAN, sg.WINSORIZED, "median"])
+def test_hist_kernel_table(gpu_ctx, rejection, norm):
+    """every k_stack_hist<REJ, NORM, 1> the host's kernel table names, reached through it: the four
+    rejections and stack_median, each without normalisation (NORM 0), additive with every
+    offset - 0.5 exact (NORM 3, the folded + 0.5), additive with one offset of 1e-30 (NORM 1) and
+    multiplicative (NORM 2).  N = 16 is the histogram path's smallest stack; W = 200 is one whole
+    128-pixel tile and a partial one.  Image and counters equal the oracle."""
+    N, H, W = 16, 6, 200
+    frames = orc.synth(N, 1, H, W, seed=31, maxshift=2)
+    sx, sy = orc.synth_shifts(N, seed=31, maxshift=2)
+    rng = np.random.default_rng(32)
+    normalize, off, mul, scale = sg.NO_NORM, None, None, None
+    if norm != "none":
+        normalize = sg.MULTIPLICATIVE if norm == "multiplicative" else sg.ADDITIVE_SCALING
+        off = np.round(rng.uniform(-60, 60, N) * 2) / 2          # half-integers: offset - 0.5 is exact
+        if norm == "additive-tiny":
+            off[5] = 1e-30
+        scale = 1.0 + rng.uniform(-0.03, 0.03, N)
+        scale[0] = 1.0
+        mul = 1.0 + rng.uniform(-0.05, 0.05, N)
+    if rejection == "median":
+        rc, ref = orc.stack_median(frames, normalize, off, mul, scale)
+        rej_ref = np.zeros((3, 2), dtype=np.uint64)
+        out, rej, _ = gpu_stack(gpu_ctx, frames, sg.MEDIAN, normalize=normalize, offset=off, mul=mul, scale=scale,
+                                max_thread=2)
+    else:
+        rc, ref, rej_ref = orc.stack_rejection(frames, rejection, sig=REJ[rejection], shiftx=sx, shifty=sy,
+                                               normalize=normalize, offset=off, mul=mul, scale=scale, max_thread=2)
+        out, rej, _ = gpu_stack(gpu_ctx, frames, sg.MEAN, rejection, REJ[rejection], sx, sy, normalize=normalize,
+                                offset=off, mul=mul, scale=scale, max_thread=2)
+    assert rc == 0
+    assert gpu_ctx.stats().path == 1
+    assert_same(out, ref, f"hist table rej={rejection} norm={norm}")
+    assert np.array_equal(rej, rej_ref), (rej, rej_ref)

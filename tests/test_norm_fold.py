@@ -4,7 +4,8 @@ The reference normalises a sample as round_to_WORD(v * scale - offset)
 (src/stacking/stacking.c:1635-1652, round_to_WORD src/core/utils.c:68-74): two double
 roundings, then (WORD)(x + 0.5) for 0 < x <= 65535.  When c = offset - 0.5 is exact, the
 kernel computes trunc(v * scale - c) instead (one double add per sample less).  The host
-enables the fold only when the TwoSum error of offset - 0.5 is zero (csrc/sg_api.cpp); this
+enables the fold only when the TwoSum error of offset - 0.5 is zero (csrc/sg_stack_plan.hpp,
+sg_plan_norm_table; tests/test_stack_plan_cpu.py runs that code itself); this
 test checks the equality over every u16 sample value for random and adversarial offsets
 (half-integers and their neighbours), and the host's exactness test itself.
 """
