@@ -6,6 +6,7 @@
  */
 #pragma once
 #include "sg_common.hpp"
+#include "sg_reg_plan.hpp"
 #include <math.h>
 #include <type_traits>
 
@@ -28,18 +29,7 @@ __device__ __forceinline__ int sg_bitrev(int x, int logn) {
 __device__ __forceinline__ int sg_pad(int i) {
 	return i + (i >> 3);
 }
-#define SG_PADN(n) ((n) + ((n) >> 3))
-/* element stride between the columns of a column-strip kernel (k_reg_cols, k_reg_cols_xpower):
- * float2 strips +4 so that the batch-minor passes (4 columns x 8 consecutive elements per 32-lane
- * group: the last FFT pass, the cross power, the inverse's first pass) and the first pass's
- * stores fall on distinct banks -- a bank model of the S = 2048 pass (64 banks for ds_read_b64,
- * 32 for ds_write_b64, MI355X_MICROARCH.md LDS) gives 1.54x the conflict-free LDS cycles against
- * 2.62x at +1, and SQ_LDS_BANK_CONFLICT of the pass was 2.05x its active LDS cycles
- * (profiles/r04r_sq_register_1.txt); double2 strips keep +1 */
-template <class C>
-__host__ __device__ constexpr int sg_col_stride(int S) {
-	return SG_PADN(S) + (sizeof(C) == 8 ? 4 : 1);
-}
+/* SG_PADN(n), the padded length, and sg_col_stride: sg_reg_plan.hpp (the host plan sizes LDS with them) */
 
 /* complex arithmetic for C = double2 (the default, every path) or float2 (the fp32 power-of-two
  * passes, whose near ties are re-run in fp64) */
@@ -460,7 +450,6 @@ __device__ __forceinline__ void sg_energy_add(unsigned long long ea, unsigned lo
 
 /* candidates of a near tie: the indices whose FFT correlation reaches max - tol, for an exact
  * integer recomputation (k_reg_exact); capped, an overflow leaves the frame unresolved */
-#define SG_CAND_CAP 64
 struct SgCand {
 	unsigned int count;
 	int idx[SG_CAND_CAP];

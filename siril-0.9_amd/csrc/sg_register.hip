@@ -418,7 +418,6 @@ __device__ __forceinline__ void sg_fft2048_wave(float2 (&v)[32], float2 *col, co
 #ifndef SG_WCOL_WPE
 #define SG_WCOL_WPE 2
 #endif
-#define SG_WCOL_CS 2120	/* LDS float2 per column: 2048 (strip) / 32 x 66 (transposes), +8 for the strip's banks */
 /* physical LDS row of strip row r in column c of a CW-column strip, so that the strip's 8-byte
  * stores (32 banks, 16-lane groups) and its 8-byte reads (64 banks, 32-lane groups, CS = 8 mod 32)
  * are both conflict-free (a 2-way conflict on the stores was 20 % of the column pass's LDS
@@ -1226,13 +1225,6 @@ k_quality_grad_s(const uint16_t *__restrict__ qbuf, int xs, int ys, const unsign
  * power-of-two passes; the cross power works on the transposed spectra directly (the mirror of
  * (r, c) is ((S - r) % S, (S - c) % S) in either layout).
  * ------------------------------------------------------------------------------------- */
-#define SG_GEN_MAXPASS 16
-struct SgGenPlan {
-	int n, npass;
-	int radix[SG_GEN_MAXPASS];
-	int bluestein, m;	/* Bluestein: convolution length m (power of two) */
-};
-
 /* cos / sin of 2 pi m / R, m < R (R = 3, 5, 7) */
 template <int R>
 __device__ __forceinline__ void sg_unit(int m, double &c, double &s) {
@@ -1662,10 +1654,6 @@ k_reg_resolve(const SgCand *__restrict__ cand, int S, int np, SgRegOut *__restri
 	out[pair] = o;
 }
 
-/* The quality estimate of `frames`, enqueued on the device's auxiliary stream (after the work
- * already on `s`, which produced d_sel) so that it runs beside the FFT passes: its kernels are
- * short and the passes leave the chip latency-bound.  reg_quality_finish waits for the sums and
- * forms the values; *launched = false when the subsample loop never runs (dval = 0, :95-98). */
 /* the estimate's buffers: qbuf (nq subsampled frames, then the frame list), acc [nq][3] + qmax [nq] */
 struct SgQBufs {
 	uint16_t *qbuf;
@@ -1776,75 +1764,6 @@ static int reg_quality_finish(sg_ctx *ctx, SgDevice &dv, int nq, bool launched, 
 	return SG_OK;
 }
 
-static int ilog2(int v) {
-	int l = 0;
-	while ((1 << l) < v)
-		l++;
-	return l;
-}
-
-/* forward full circle exp(-2 pi i k / n), k < n, then its conjugate (the inverse), as the
- * device transforms read them (sg_twiddle).  Power of two: the half circle, negated exactly
- * for k >= n/2; otherwise every k directly. */
-static void make_twiddles(int n, std::vector<double> &tw) {
-	tw.assign(4 * (size_t)n, 0.0);
-	const bool pow2 = (n & (n - 1)) == 0;
-	for (int k = 0; k < (pow2 ? n / 2 : n); k++) {
-		const double a = -2.0 * M_PI * (double)k / (double)n;
-		const double c = cos(a), sn = sin(a);
-		const int nk = pow2 ? 2 : 1;
-		const int kk[2] = {k, k + n / 2};
-		const double sg[2] = {1.0, -1.0};
-		for (int h = 0; h < nk; h++) {
-			tw[2 * kk[h]] = sg[h] * c;
-			tw[2 * kk[h] + 1] = sg[h] * sn;
-			tw[2 * (n + kk[h])] = sg[h] * c;
-			tw[2 * (n + kk[h]) + 1] = -(sg[h] * sn);
-		}
-	}
-}
-
-/* radices of an n-point mixed-radix plan (8, 4, 2, 3, 5, 7); false: a prime factor > 7 */
-static bool make_plan(int n, SgGenPlan &pl) {
-	memset(&pl, 0, sizeof pl);
-	pl.n = n;
-	int r = n;
-	const int rad[6] = {8, 4, 2, 3, 5, 7};
-	for (int q = 0; q < 6; q++)
-		while (r % rad[q] == 0 && pl.npass < SG_GEN_MAXPASS) {
-			pl.radix[pl.npass++] = rad[q];
-			r /= rad[q];
-		}
-	return r == 1;
-}
-
-/* in-place radix-2 complex DFT on the host (Bluestein's chirp spectrum, computed once per call) */
-static void host_fft_pow2(std::vector<double> &re, std::vector<double> &im, int n) {
-	for (int i = 1, j = 0; i < n; i++) {
-		int bit = n >> 1;
-		for (; j & bit; bit >>= 1)
-			j ^= bit;
-		j ^= bit;
-		if (i < j) {
-			std::swap(re[i], re[j]);
-			std::swap(im[i], im[j]);
-		}
-	}
-	for (int len = 2; len <= n; len <<= 1) {
-		for (int i = 0; i < n; i += len)
-			for (int k = 0; k < len / 2; k++) {
-				const double a = -2.0 * M_PI * (double)k / (double)len;
-				const double wr = cos(a), wi = sin(a);
-				const double xr = re[i + k + len / 2], xi = im[i + k + len / 2];
-				const double vr = xr * wr - xi * wi, vi = xr * wi + xi * wr;
-				re[i + k + len / 2] = re[i + k] - vr;
-				im[i + k + len / 2] = im[i + k] - vi;
-				re[i + k] += vr;
-				im[i + k] += vi;
-			}
-	}
-}
-
 static int reg_dft_device(sg_ctx *ctx, int dev_index, const uint16_t *d_sel_p, int64_t fpitch, int64_t rpitch,
 		int nframes, int S, int ref_image, const int *included, int *shiftx, int *shifty, double *quality, void *stream,
 		bool normalize_q);
@@ -1873,31 +1792,661 @@ extern "C" int sg_register_dft_u16_device_pitched(sg_ctx *ctx, int dev_index, co
 			quality, stream, !raw_quality);
 }
 
+/* the plan counts its layouts in these sizes (sg_reg_plan.hpp) */
+static_assert(sizeof(SgBest) == SG_REG_SIZEOF_BEST && sizeof(SgRegOut) == SG_REG_SIZEOF_OUT &&
+		sizeof(SgCand) == SG_REG_SIZEOF_CAND && sizeof(sg_c64) == SG_REG_SIZEOF_C64 &&
+		sizeof(float2) == SG_REG_SIZEOF_C32, "sg_reg_plan.hpp sizes its byte layouts with these");
+
+/* SgRegKernel -> the kernel whose dynamic LDS limit is raised */
+static const void *const SG_REG_LDS_KERNELS[SG_RK_COUNT] = {
+	(const void *)k_gen_cols_xpower, (const void *)k_gen_rows<true>, (const void *)k_gen_rows<false>,
+	(const void *)k_reg_cols<sg_c64, 8>, (const void *)k_reg_rows_fwd_half<sg_c64>,
+	(const void *)k_reg_rows_inv_half_argmax<sg_c64, false>, (const void *)k_reg_rows_inv_half_argmax<sg_c64, true>,
+	(const void *)k_reg_cols_xpower<sg_c64, 8>, (const void *)k_reg_rows_fwd_half<float2>,
+	(const void *)k_reg_rows_inv_half_argmax<float2, false>, (const void *)k_reg_cols<float2, 8>,
+	(const void *)k_reg_cols<float2, 16>,
+	/* SG_RK_XPOWER32 + SgRegCols32 */
+	(const void *)k_reg_cols_xpower<float2, 8>, (const void *)k_reg_cols_xpower<float2, 8, 8>,
+	(const void *)k_reg_cols_xpower<float2, 16>, (const void *)k_reg_cols_xpower_w<true, 4>,
+	(const void *)k_reg_cols_xpower_w<true, 8>, (const void *)k_reg_cols_xpower_w<false, 4>,
+	(const void *)k_reg_cols_fwd_perm_w, (const void *)k_reg_rows_fwd_half_w<false>,
+	(const void *)k_reg_rows_fwd_half_w<true>, (const void *)k_reg_rows_inv_half_w};
+
+/* kernel instances with one argument list, indexed by the plan's decisions */
+typedef decltype(&k_gen_rows<true>) SgGenRowsFn;
+static constexpr SgGenRowsFn SG_GEN_ROWS_KERNELS[2] = {k_gen_rows<false>, k_gen_rows<true>};	/* [bluestein] */
+typedef decltype(&k_reg_rows_inv_half_argmax<sg_c64, false>) SgInv64Fn;
+static constexpr SgInv64Fn SG_INV64_KERNELS[2] = {	/* [candidates] */
+	k_reg_rows_inv_half_argmax<sg_c64, false>, k_reg_rows_inv_half_argmax<sg_c64, true>};
+typedef decltype(&k_reg_cols<float2, 8>) SgCols32Fn;
+static constexpr SgCols32Fn SG_COLS32_KERNELS[2] = {k_reg_cols<float2, 8>, k_reg_cols<float2, 16>};	/* [ept32 == 16] */
+typedef decltype(&k_reg_cols_xpower<float2, 8>) SgXpower32Fn;
+static constexpr SgXpower32Fn SG_XPOWER32_KERNELS[3] = {	/* [SgRegCols32]: the block-level forms */
+	k_reg_cols_xpower<float2, 8>, k_reg_cols_xpower<float2, 8, 8>, k_reg_cols_xpower<float2, 16>};
+typedef decltype(&k_reg_cols_xpower_w<true, 4>) SgXpowerWFn;
+static constexpr SgXpowerWFn SG_XPOWER_WP_KERNELS[2] = {	/* [SgRegCols32 - SG_COLS32_WAVE4_PERM]: the permuted-spectrum forms */
+	k_reg_cols_xpower_w<true, 4>, k_reg_cols_xpower_w<true, 8>};
+
+/* one registration call on its way through the launch steps */
+struct SgRegRun {
+	sg_ctx *ctx;
+	SgDevice &dv;
+	hipStream_t s;
+	const SgRegPlan &pl;
+	SgSel d_sel;
+	/* tables (reg_tw, reg_tw32) */
+	SgGenTables tbl;
+	const sg_c64 *tw;
+	const float2 *tw32;
+	/* reg_spec: the reference spectrum in fp64, fp32 and (wave-level passes) fp32 lane order;
+	 * reg_work: the pair planes (generic path: work2 = the transposed planes) */
+	sg_c64 *spec, *work, *work2;
+	float2 *spec32, *work32, *specp32;
+	/* reg_best: row partials, per-pair results, the pair table and the re-runs' subset of it, the
+	 * frames' energies (energy: the main passes, each frame once; energy2: the re-runs'), the
+	 * near-tie candidates of one batch, the re-runs' results */
+	SgBest *best;
+	SgRegOut *d_out, *d_res2;
+	int *d_fa, *d_fb, *d_fa2, *d_fb2;
+	unsigned long long *energy, *energy2;
+	SgCand *cand;
+	/* the pinned block: the pair table going up, the results coming back */
+	int *pfab;
+	SgRegOut *pout;
+	std::vector<SgRegOut> hout;	/* the pairs' results on the host */
+	SgQBufs qfb;			/* the folded quality estimate's buffers */
+	bool ref_pending;	/* set by reg_ref_spectrum32 (the spectrum is on its own stream); cleared by the first reg_half32, which waits for it, or behind the batch loop */
+	bool q_deferred;	/* set by reg_quality_start (SG_REG_Q_DEFERRED); cleared by the first reg_half32, which launches the estimate */
+	bool q_fold_last;	/* set by reg_main_batches for every batch (true on the last); read by reg_half32: the gradient follows */
+	int q_qbase;		/* set by reg_main_batches for every batch (its first frame's entry of qframes); read by reg_half32 */
+	bool q_launched;	/* set by reg_quality_launch or reg_half32's gradient, never cleared; read by reg_quality_readback */
+};
+
+/* tables: twiddles exp(-2 pi i k / S); generic path: for Bluestein the m-point twiddles, the
+ * chirp c_j = exp(-i pi j^2 / S) and FFT_m(b).  They depend on S (and the path) only: uploaded
+ * when either changes */
+static int reg_upload_tables64(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	const SgRegPlan &pl = r.pl;
+	const bool blue = pl.gen.bluestein != 0;
+	if (dv.reg_tab_S != pl.S || dv.reg_tab_generic != (int)pl.generic) {
+		std::vector<double> tw, twm, ch, bh;
+		make_twiddles(pl.S, tw);
+		if (blue) {
+			make_twiddles(pl.gen.m, twm);
+			make_bluestein(pl.S, (size_t)pl.gen.m, ch, bh);
+		}
+		dv.reg_tab_S = 0;
+		HIPCHK(ensure(dv.reg_tw, sizeof(double) * pl.tab_total));
+		double *d = (double *)dv.reg_tw.p;
+		HIPCHK(hipMemcpyAsync(d, tw.data(), sizeof(double) * pl.n_tw, hipMemcpyHostToDevice, r.s));
+		if (blue) {
+			HIPCHK(hipMemcpyAsync(d + pl.n_tw, twm.data(), sizeof(double) * pl.n_twm, hipMemcpyHostToDevice, r.s));
+			HIPCHK(hipMemcpyAsync(d + pl.n_tw + pl.n_twm, ch.data(), sizeof(double) * pl.n_ch, hipMemcpyHostToDevice, r.s));
+			HIPCHK(hipMemcpyAsync(d + pl.n_tw + pl.n_twm + pl.n_ch, bh.data(), sizeof(double) * pl.n_bh,
+					hipMemcpyHostToDevice, r.s));
+		}
+		HIPCHK(hipStreamSynchronize(r.s));	/* the host vectors die here */
+		dv.reg_tab_S = pl.S;
+		dv.reg_tab_generic = (int)pl.generic;
+	}
+	double *d = (double *)dv.reg_tw.p;
+	memset(&r.tbl, 0, sizeof r.tbl);
+	r.tbl.tw = (const sg_c64 *)d;
+	if (blue) {
+		r.tbl.twm = (const sg_c64 *)(d + pl.n_tw);
+		r.tbl.chirp = (const sg_c64 *)(d + pl.n_tw + pl.n_twm);
+		r.tbl.bhat = (const sg_c64 *)(d + pl.n_tw + pl.n_twm + pl.n_ch);
+	}
+	r.tw = r.tbl.tw;
+	return SG_OK;
+}
+
+/* fp32 twiddles, rounded from the fp64 table; uploaded when S changes */
+static int reg_upload_tables32(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	r.tw32 = nullptr;
+	if (!r.pl.fp32)
+		return SG_OK;
+	if (dv.reg_tw32_S != r.pl.S) {
+		dv.reg_tw32_S = 0;
+		HIPCHK(ensure(dv.reg_tw32, 2 * (size_t)r.pl.S * sizeof(float2)));
+		std::vector<float> t32;
+		make_twiddles32(r.pl.S, t32);
+		HIPCHK(hipMemcpyAsync(dv.reg_tw32.p, t32.data(), sizeof(float) * t32.size(), hipMemcpyHostToDevice, r.s));
+		HIPCHK(hipStreamSynchronize(r.s));
+		dv.reg_tw32_S = r.pl.S;
+	}
+	r.tw32 = (const float2 *)dv.reg_tw32.p;
+	return SG_OK;
+}
+
+static void reg_raise_lds(const SgRegPlan &pl) {
+	for (const SgRegLdsAttr &a : pl.lds_attrs)
+		(void)hipFuncSetAttribute(SG_REG_LDS_KERNELS[a.kernel], hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes);
+}
+
+/* device workspace: reg_spec, reg_work and reg_best carved at the plan's offsets, the energies zeroed */
+static int reg_carve_workspace(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	const SgRegPlan &pl = r.pl;
+	const int NP = pl.NP;
+	HIPCHK(ensure(dv.reg_spec, pl.spec_bytes));
+	HIPCHK(ensure(dv.reg_work, pl.work_bytes));
+	HIPCHK(ensure(dv.reg_best, pl.ws));
+	char *wsp = (char *)dv.reg_best.p;
+	r.spec = (sg_c64 *)dv.reg_spec.p;
+	r.work = (sg_c64 *)dv.reg_work.p;
+	r.spec32 = (float2 *)((char *)dv.reg_spec.p + pl.plane * sizeof(sg_c64));
+	r.work32 = (float2 *)dv.reg_work.p;
+	r.specp32 = pl.specp_on ? r.spec32 + pl.plane : nullptr;
+	r.work2 = r.work + (size_t)pl.Bc * pl.plane;	/* generic path: transposed planes */
+	r.best = (SgBest *)wsp;
+	r.d_out = (SgRegOut *)(wsp + pl.o_out);
+	r.d_res2 = (SgRegOut *)(wsp + pl.o_res2);
+	r.d_fa = (int *)(wsp + pl.o_fab);
+	r.d_fb = r.d_fa + (NP + 1);
+	r.d_fa2 = r.d_fb + (NP + 1);
+	r.d_fb2 = r.d_fa2 + (NP + 1);
+	r.energy = (unsigned long long *)(wsp + pl.o_en);
+	r.energy2 = r.energy + pl.nframes;
+	r.cand = (SgCand *)(wsp + pl.o_cand);
+	HIPCHK(hipMemsetAsync(r.energy, 0, sizeof(unsigned long long) * 2 * pl.nframes, r.s));
+	return SG_OK;
+}
+
+/* aux2: the stream of a concurrent reference spectrum */
+static int reg_ref_stream(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	if (r.pl.ref_conc && !dv.aux2) {
+		HIPCHK(hipStreamCreateWithFlags(&dv.aux2, hipStreamNonBlocking));
+		for (int k = 0; k < 2; k++)
+			HIPCHK(hipEventCreateWithFlags(&dv.aux2_ev[k], hipEventDisableTiming));
+	}
+	return SG_OK;
+}
+
+/* the pair table goes up, and the results come back, through a pinned block (the previous
+ * call's copies are done: every call ends on a stream synchronize) */
+static int reg_upload_pairs(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	const SgRegPlan &pl = r.pl;
+	const int NP = pl.NP;
+	r.hout.resize((size_t)NP);
+	if (dv.reg_pin_n < pl.pin_bytes) {
+		if (dv.reg_pin)
+			(void)hipHostFree(dv.reg_pin);
+		dv.reg_pin = nullptr;
+		dv.reg_pin_n = 0;
+		HIPCHK(hipHostMalloc(&dv.reg_pin, pl.pin_bytes));
+		dv.reg_pin_n = pl.pin_bytes;
+	}
+	r.pfab = (int *)dv.reg_pin;
+	r.pout = (SgRegOut *)((char *)dv.reg_pin + pl.pin_res);
+	memcpy(r.pfab, pl.hfa.data(), sizeof(int) * (NP + 1));
+	memcpy(r.pfab + (NP + 1), pl.hfb.data(), sizeof(int) * (NP + 1));
+	HIPCHK(hipMemcpyAsync(r.d_fa, r.pfab, sizeof(int) * 2 * (NP + 1), hipMemcpyHostToDevice, r.s));	/* d_fb = d_fa + NP + 1 */
+	return SG_OK;
+}
+
+/* the quality estimate on the aux stream, queued behind the main stream's table uploads and
+ * fills (queued ahead of them, its long-running workgroups held the fills' single workgroup
+ * back 0.2 ms, profiles/r05m_*) */
+static int reg_quality_start(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	if (pl.qroute == SG_REG_Q_FOLDED) {	/* the sums zeroed on the call's stream, ahead of every forward row launch */
+		const int nq = (int)pl.qframes.size(), xs = (pl.S - 1) / 3;
+		if (int rc = reg_quality_buffers(ctx, r.dv, nq, xs, xs, r.qfb))
+			return rc;
+		HIPCHK(hipMemsetAsync(r.qfb.acc, 0, (size_t)nq * (3 * sizeof(unsigned long long) + sizeof(unsigned int)), r.s));
+	} else if (pl.qroute == SG_REG_Q_DEFERRED) {
+		r.q_deferred = true;
+	} else {
+		return reg_quality_launch(ctx, r.dv, r.s, r.d_sel, pl.S, pl.qframes, &r.q_launched);
+	}
+	return SG_OK;
+}
+
+/* the generic row kernel over np pairs' rows of `data` */
+static void reg_gen_rows(const SgRegRun &r, const int *fa, const int *fb, int np, sg_c64 *data, int mode, int inverse,
+		unsigned long long *en, const SgRegOut *res, SgCand *cand) {
+	const SgRegPlan &pl = r.pl;
+	hipLaunchKernelGGL(SG_GEN_ROWS_KERNELS[pl.gen.bluestein], dim3(pl.S, np), dim3(pl.gen_thr), pl.gen_lds, r.s, r.d_sel,
+			fa, fb, data, pl.S, pl.gen, r.tbl, mode, inverse, en, r.best, res, cand);
+}
+
+/* the wave-level forward rows of np pairs (or, np = 1, of the reference) into `out` */
+static void reg_fwd_w_launch(const SgRegRun &r, hipStream_t st, const int *fa, const int *fb, int np, float2 *out,
+		unsigned long long *en, int rows, int qbase) {
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S, qfold = pl.qfold;
+	if (qfold) {
+		const int waves = (S + qfold - 1) / qfold;
+		hipLaunchKernelGGL(k_reg_rows_fwd_half_w<true>, dim3((waves + 3) / 4, np), dim3(256), pl.wcol_lds, st, r.d_sel, fa,
+				fb, r.tw32, out, en, qfold, r.qfb.qbuf, r.qfb.qmax, qbase);
+	} else {
+		hipLaunchKernelGGL(k_reg_rows_fwd_half_w<false>, dim3(S / 4 / rows, np), dim3(256), pl.wcol_lds, st, r.d_sel, fa,
+				fb, r.tw32, out, en, rows, (uint16_t *)nullptr, (unsigned int *)nullptr, 0);
+	}
+}
+
+/* fp64 reference spectrum of the half-spectrum passes, its energy into `en` */
+static int reg_ref_spectrum64(SgRegRun &r, unsigned long long *en) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S, NP = pl.NP;
+	hipLaunchKernelGGL(k_reg_rows_fwd_half<sg_c64>, dim3(S / pl.rpb, 1), dim3(pl.row_thr), pl.row_lds, r.s, r.d_sel,
+			r.d_fa + NP, r.d_fb + NP, S, r.tw, r.spec, en, pl.rpb);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL((k_reg_cols<sg_c64, 8>), dim3(S / 2 / pl.CWh, 1), dim3(pl.colh_thr), pl.colh_lds, r.s, r.spec, S,
+			pl.logS, pl.CWh, r.tw, 0, pl.xcdmap);
+	HIPCHK(hipGetLastError());
+	return SG_OK;
+}
+
+/* fp32 reference spectrum on its own stream beside the first batch's forward rows (which do
+ * not read it; the batch's column pass waits for it).  One workgroup per CU at most: run
+ * alone it is 0.27 ms of latency-bound passes ahead of every pair (profiles/r05l_*) */
+static int reg_ref_spectrum32(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S, NP = pl.NP;
+	hipStream_t rs = r.s;
+	if (pl.ref_conc) {
+		HIPCHK(hipEventRecord(dv.aux2_ev[0], r.s));
+		HIPCHK(hipStreamWaitEvent(dv.aux2, dv.aux2_ev[0], 0));
+		rs = dv.aux2;
+	}
+	if (r.specp32) {	/* wave-level passes: one row per wave, the columns straight into lane order */
+		reg_fwd_w_launch(r, rs, r.d_fa + NP, r.d_fb + NP, 1, r.spec32, r.energy, 1, 0);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_reg_cols_fwd_perm_w, dim3(S / 2 / 4), dim3(256), pl.wcol_lds, rs, r.spec32, r.specp32, r.tw32);
+	} else {
+		hipLaunchKernelGGL(k_reg_rows_fwd_half<float2>, dim3(S / pl.rpb, 1), dim3(pl.row_thr), pl.row_lds32, rs, r.d_sel,
+				r.d_fa + NP, r.d_fb + NP, S, r.tw32, r.spec32, r.energy, pl.rpb);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(SG_COLS32_KERNELS[pl.ept32 == 16], dim3(S / 2 / pl.CW32, 1), dim3(pl.colh_thr32), pl.colh_lds32,
+				rs, r.spec32, S, pl.logS, pl.CW32, r.tw32, 0, pl.xcdmap);
+	}
+	if (pl.ref_conc) {
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipEventRecord(dv.aux2_ev[1], dv.aux2));
+		r.ref_pending = true;
+	}
+	HIPCHK(hipGetLastError());
+	return SG_OK;
+}
+
+/* generic reference spectrum: rows, transpose, rows (transposed layout) */
+static int reg_ref_spectrum_gen(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int NP = pl.NP;
+	reg_gen_rows(r, r.d_fa + NP, r.d_fb + NP, 1, r.work, (int)SG_GEN_FWD_U16, 0, r.energy, nullptr, nullptr);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_gen_transpose, dim3(pl.tgrid, pl.tgrid, 1), dim3(32, 8), 0, r.s, (const sg_c64 *)r.work, r.spec,
+			pl.S);
+	HIPCHK(hipGetLastError());
+	reg_gen_rows(r, r.d_fa + NP, r.d_fb + NP, 1, r.spec, (int)SG_GEN_C2C, 0, r.energy, nullptr, nullptr);
+	HIPCHK(hipGetLastError());
+	return SG_OK;
+}
+
+/* generic passes up to the cross power's inverse: transposed spectrum of the rows of `fa`
+ * / `fb` pairs -> `work` holds the pairs' inverse column transforms in row layout */
+static int reg_gen_forward(SgRegRun &r, const int *fa, const int *fb, int np, unsigned long long *en) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S;
+	const dim3 tgrid(pl.tgrid, pl.tgrid, np);
+	reg_gen_rows(r, fa, fb, np, r.work, (int)SG_GEN_FWD_U16, 0, en, nullptr, nullptr);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(k_gen_transpose, tgrid, dim3(32, 8), 0, r.s, (const sg_c64 *)r.work, r.work2, S);
+	HIPCHK(hipGetLastError());
+	if (pl.gen_fuse) {	/* forward columns + cross power + inverse columns in one pass */
+		hipLaunchKernelGGL(k_gen_cols_xpower, dim3(S / 2 + 1, np), dim3(2 * pl.gen_thr), 2 * pl.gen_lds, r.s, r.work2,
+				(const sg_c64 *)r.spec, S, pl.gen, r.tw);
+		HIPCHK(hipGetLastError());
+	} else {
+		reg_gen_rows(r, fa, fb, np, r.work2, (int)SG_GEN_C2C, 0, en, nullptr, nullptr);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_gen_xpower, dim3(1024, np), dim3(256), 0, r.s, r.work2, (const sg_c64 *)r.spec, S);
+		HIPCHK(hipGetLastError());
+		reg_gen_rows(r, fa, fb, np, r.work2, (int)SG_GEN_C2C, 1, en, nullptr, nullptr);
+		HIPCHK(hipGetLastError());
+	}
+	hipLaunchKernelGGL(k_gen_transpose, tgrid, dim3(32, 8), 0, r.s, (const sg_c64 *)r.work2, r.work, S);
+	HIPCHK(hipGetLastError());
+	return SG_OK;
+}
+
+/* fp64 half-spectrum passes of the pairs (fa, fb)[0, np) against the fp64 reference spectrum:
+ * `cand` 0 = top-2 arg-max into best, 1 = near-tie candidates of the results `res` */
+static int reg_half64(SgRegRun &r, const int *fa, const int *fb, int np, unsigned long long *en, int cand,
+		const SgRegOut *res) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S;
+	hipLaunchKernelGGL(k_reg_rows_fwd_half<sg_c64>, dim3(S / pl.rpb, np), dim3(pl.row_thr), pl.row_lds, r.s, r.d_sel, fa, fb,
+			S, r.tw, r.work, en, pl.rpb);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL((k_reg_cols_xpower<sg_c64, 8>), dim3(S / pl.CWh, np), dim3(pl.colh_thr), pl.colh_lds, r.s, r.work,
+			(const sg_c64 *)r.spec, S, pl.CWh, r.tw, pl.xcdmap, pl.pb);
+	HIPCHK(hipGetLastError());
+	hipLaunchKernelGGL(SG_INV64_KERNELS[cand], dim3(S, np), dim3(pl.row_thr), pl.row_lds, r.s, (const sg_c64 *)r.work, S,
+			r.tw, r.best, cand ? res : (const SgRegOut *)nullptr, cand ? r.cand : (SgCand *)nullptr);
+	HIPCHK(hipGetLastError());
+	return SG_OK;
+}
+
+/* what the first / last batch's fp32 forward rows are followed by: the deferred quality estimate,
+ * the wait for the reference spectrum's stream, the folded estimate's gradient */
+static int reg_half32_after_rows(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	const SgRegPlan &pl = r.pl;
+	if (r.q_deferred) {	/* SG_REG_QAFTER: the quality estimate beside the column pass instead */
+		r.q_deferred = false;
+		if (int rc = reg_quality_launch(ctx, dv, r.s, r.d_sel, pl.S, pl.qframes, &r.q_launched))
+			return rc;
+	}
+	if (r.ref_pending) {	/* the reference spectrum, from its stream */
+		HIPCHK(hipStreamWaitEvent(r.s, dv.aux2_ev[1], 0));
+		r.ref_pending = false;
+	}
+	if (pl.qfold && r.q_fold_last) {	/* every frame subsampled (the reference's rows waited for above) */
+		const int nq = (int)pl.qframes.size(), xs = (pl.S - 1) / 3;
+		HIPCHK(hipEventRecord(dv.aux_ev[1], r.s));
+		HIPCHK(hipStreamWaitEvent(dv.aux, dv.aux_ev[1], 0));
+		if (int rc = reg_quality_grad(ctx, dv, nq, xs, xs, r.qfb))
+			return rc;
+		r.q_launched = true;
+	}
+	return SG_OK;
+}
+
+/* fp32 half-spectrum passes of the pairs (fa, fb)[0, np): top-2 arg-max into best */
+static int reg_half32(SgRegRun &r, const int *fa, const int *fb, int np, unsigned long long *en) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S;
+	if (pl.wcol)
+		reg_fwd_w_launch(r, r.s, fa, fb, np, r.work32, en, pl.rpw, r.q_qbase);
+	else
+		hipLaunchKernelGGL(k_reg_rows_fwd_half<float2>, dim3(S / pl.rpb, np), dim3(pl.row_thr), pl.row_lds32, r.s, r.d_sel,
+				fa, fb, S, r.tw32, r.work32, en, pl.rpb);
+	HIPCHK(hipGetLastError());
+	if (int rc = reg_half32_after_rows(r))
+		return rc;
+	if (pl.cols32 == SG_COLS32_WAVE4_PERM || pl.cols32 == SG_COLS32_WAVE8_PERM) {	/* S = 2048: the wave-level column pass (SG_REG_WCOL=0: the block-level one, A/B) */
+		const int cw = pl.cols32 == SG_COLS32_WAVE8_PERM ? 8 : 4;	/* 8-column strips: 64-B row segments, one workgroup per CU */
+		hipLaunchKernelGGL(SG_XPOWER_WP_KERNELS[pl.cols32 - SG_COLS32_WAVE4_PERM], dim3(S / cw, np), dim3(64 * cw),
+				cw / 4 * pl.wcol_lds, r.s, r.work32, (const float2 *)r.spec32, (const float2 *)r.specp32, r.tw32, pl.xcdmap);
+	} else if (pl.cols32 == SG_COLS32_WAVE4_LDS) {
+		hipLaunchKernelGGL((k_reg_cols_xpower_w<false, 4>), dim3(S / 4, np), dim3(256), pl.wcol_lds, r.s, r.work32,
+				(const float2 *)r.spec32, (const float2 *)nullptr, r.tw32, pl.xcdmap);
+	} else {	/* 8 elements per thread, 8 at 64 VGPRs (default, SG_REG_COLOCC=1), or 16 */
+		hipLaunchKernelGGL(SG_XPOWER32_KERNELS[pl.cols32], dim3(S / pl.CW32, np), dim3(pl.colh_thr32), pl.colh_lds32, r.s,
+				r.work32, (const float2 *)r.spec32, S, pl.CW32, r.tw32, pl.xcdmap, 1);
+	}
+	HIPCHK(hipGetLastError());
+	if (pl.wcol)
+		hipLaunchKernelGGL(k_reg_rows_inv_half_w, dim3(S / 4, np), dim3(256), pl.wcol_lds, r.s, (const float2 *)r.work32,
+				r.tw32, r.best);
+	else
+		hipLaunchKernelGGL((k_reg_rows_inv_half_argmax<float2, false>), dim3(S, np), dim3(pl.row_thr), pl.row_lds32, r.s,
+				(const float2 *)r.work32, S, r.tw32, r.best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
+	HIPCHK(hipGetLastError());
+	return SG_OK;
+}
+
+/* reference spectrum R = FFT2(ref) (half layout: the A' half only; generic: transposed) */
+static int reg_ref_spectrum(SgRegRun &r) {
+	if (r.pl.generic)
+		return reg_ref_spectrum_gen(r);
+	if (r.pl.fp32)
+		return reg_ref_spectrum32(r);
+	return reg_ref_spectrum64(r, r.energy);
+}
+
+/* the pairs in batches of B: their passes, then per pair the shifts and the near-tie flags;
+ * the results come back through the pinned block */
+static int reg_main_batches(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S, npairs_total = pl.npairs_total;
+	for (int p0 = 0; p0 < npairs_total; p0 += pl.B) {
+		const int np = npairs_total - p0 < pl.B ? npairs_total - p0 : pl.B;
+		if (pl.generic) {
+			if (int rc = reg_gen_forward(r, r.d_fa + p0, r.d_fb + p0, np, r.energy))
+				return rc;
+			reg_gen_rows(r, r.d_fa + p0, r.d_fb + p0, np, r.work, (int)SG_GEN_INV_ARGMAX, 1, r.energy, nullptr, nullptr);
+		} else if (pl.fp32) {
+			r.q_qbase = 1 + 2 * p0;	/* qframes = ref, todo...: pair k's frames are entries 1 + 2k, 2 + 2k */
+			r.q_fold_last = p0 + np >= npairs_total;
+			if (int rc = reg_half32(r, r.d_fa + p0, r.d_fb + p0, np, r.energy))
+				return rc;
+		} else {
+			if (int rc = reg_half64(r, r.d_fa + p0, r.d_fb + p0, np, r.energy, 0, nullptr))
+				return rc;
+		}
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_reg_final, dim3(np), dim3(256), 0, r.s, (const SgBest *)r.best, S, S /* row partials per pair */,
+				(const int *)r.d_fa + p0, (const int *)r.d_fb + p0, pl.ref_image, (const unsigned long long *)r.energy,
+				pl.tol_main, r.d_out + p0);
+		HIPCHK(hipGetLastError());
+	}
+	if (r.ref_pending) {
+		HIPCHK(hipStreamWaitEvent(r.s, r.dv.aux2_ev[1], 0));
+		r.ref_pending = false;
+	}
+	if (npairs_total > 0)
+		HIPCHK(hipMemcpyAsync(r.pout, r.d_out, sizeof(SgRegOut) * npairs_total, hipMemcpyDeviceToHost, r.s));
+	HIPCHK(hipStreamSynchronize(r.s));
+	if (npairs_total > 0)
+		memcpy(r.hout.data(), r.pout, sizeof(SgRegOut) * npairs_total);
+	return SG_OK;
+}
+
+/* the pairs with a near tie (the runner-up within the tolerance of the maximum) */
+static void reg_ambiguous(const SgRegRun &r, std::vector<int> &amb) {
+	amb.clear();
+	for (int k = 0; k < r.pl.npairs_total; k++)
+		if (r.hout[k].amb[0] == 1 || r.hout[k].amb[1] == 1)
+			amb.push_back(k);
+}
+
+/* the pairs `amb` and their results so far as a pair table of their own (d_fa2, d_fb2, d_res2) */
+static int reg_upload_subset(SgRegRun &r, const std::vector<int> &amb, std::vector<SgRegOut> &ares) {
+	sg_ctx *ctx = r.ctx;
+	const int na = (int)amb.size();
+	std::vector<int> afa(na), afb(na);
+	ares.resize(na);
+	for (int i = 0; i < na; i++) {
+		afa[i] = r.pl.hfa[amb[i]];
+		afb[i] = r.pl.hfb[amb[i]];
+		ares[i] = r.hout[amb[i]];
+	}
+	HIPCHK(hipMemcpyAsync(r.d_fa2, afa.data(), sizeof(int) * na, hipMemcpyHostToDevice, r.s));
+	HIPCHK(hipMemcpyAsync(r.d_fb2, afb.data(), sizeof(int) * na, hipMemcpyHostToDevice, r.s));
+	HIPCHK(hipMemcpyAsync(r.d_res2, ares.data(), sizeof(SgRegOut) * na, hipMemcpyHostToDevice, r.s));
+	HIPCHK(hipStreamSynchronize(r.s));	/* the host vectors die here */
+	return SG_OK;
+}
+
+/* the subset's results back into the pairs' */
+static int reg_download_subset(SgRegRun &r, const std::vector<int> &amb, std::vector<SgRegOut> &ares) {
+	sg_ctx *ctx = r.ctx;
+	const int na = (int)amb.size();
+	HIPCHK(hipMemcpyAsync(ares.data(), r.d_res2, sizeof(SgRegOut) * na, hipMemcpyDeviceToHost, r.s));
+	HIPCHK(hipStreamSynchronize(r.s));
+	for (int i = 0; i < na; i++)
+		r.hout[amb[i]] = ares[i];
+	return SG_OK;
+}
+
+/* near ties after fp32 passes: the fp64 reference spectrum, then the pairs' fp64 passes and a
+ * fresh arg-max at the fp64 tolerance */
+static int reg_rerun_fp64(SgRegRun &r, std::vector<int> &amb, std::vector<SgRegOut> &ares) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	if (int rc = reg_upload_subset(r, amb, ares))
+		return rc;
+	if (int rc = reg_ref_spectrum64(r, r.energy2))
+		return rc;
+	const int na = (int)amb.size();
+	for (int p0 = 0; p0 < na; p0 += pl.B64) {
+		const int np = na - p0 < pl.B64 ? na - p0 : pl.B64;
+		if (int rc = reg_half64(r, r.d_fa2 + p0, r.d_fb2 + p0, np, r.energy2, 0, nullptr))
+			return rc;
+		/* `energy`, not `energy2`, on purpose: the tolerance takes each frame's sum of squares once,
+		 * which the main passes left in energy.  energy2 only keeps the re-runs' forward rows from
+		 * adding the same rows to energy a second time (a frame re-run here and again for its
+		 * candidates has twice its energy there); no kernel reads it */
+		hipLaunchKernelGGL(k_reg_final, dim3(np), dim3(256), 0, r.s, (const SgBest *)r.best, pl.S, pl.S,
+				(const int *)r.d_fa2 + p0, (const int *)r.d_fb2 + p0, pl.ref_image, (const unsigned long long *)r.energy,
+				-32, r.d_res2 + p0);
+		HIPCHK(hipGetLastError());
+	}
+	if (int rc = reg_download_subset(r, amb, ares))
+		return rc;
+	r.dv.stats.reg_fp64_reruns += (uint64_t)na;
+	reg_ambiguous(r, amb);
+	return SG_OK;
+}
+
+/* what is still a near tie in fp64: every index within the tolerance is listed, their exact
+ * integer correlations computed and the largest taken (lowest index among exact equals) */
+static int reg_resolve_exact(SgRegRun &r, const std::vector<int> &amb, std::vector<SgRegOut> &ares) {
+	sg_ctx *ctx = r.ctx;
+	const SgRegPlan &pl = r.pl;
+	const int S = pl.S;
+	if (int rc = reg_upload_subset(r, amb, ares))
+		return rc;
+	const int na = (int)amb.size();
+	for (int p0 = 0; p0 < na; p0 += pl.B64) {
+		const int np = na - p0 < pl.B64 ? na - p0 : pl.B64;
+		HIPCHK(hipMemsetAsync(r.cand, 0, sizeof(SgCand) * 2 * np, r.s));
+		if (pl.generic) {
+			if (int rc = reg_gen_forward(r, r.d_fa2 + p0, r.d_fb2 + p0, np, r.energy2))
+				return rc;
+			reg_gen_rows(r, r.d_fa2 + p0, r.d_fb2 + p0, np, r.work, (int)SG_GEN_INV_CAND, 1, r.energy2,
+					(const SgRegOut *)(r.d_res2 + p0), r.cand);
+		} else {
+			/* the fp64 spectrum exists on the fp64 half path, and after the fp64 re-run */
+			if (int rc = reg_half64(r, r.d_fa2 + p0, r.d_fb2 + p0, np, r.energy2, 1, (const SgRegOut *)(r.d_res2 + p0)))
+				return rc;
+		}
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_reg_exact, dim3(SG_CAND_CAP, 2 * np), dim3(256), 0, r.s, r.d_sel, (const int *)r.d_fa2 + p0,
+				(const int *)r.d_fb2 + p0, pl.ref_image, S, r.cand);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_reg_resolve, dim3((np + 63) / 64), dim3(64), 0, r.s, (const SgCand *)r.cand, S, np,
+				r.d_res2 + p0);
+		HIPCHK(hipGetLastError());
+	}
+	return reg_download_subset(r, amb, ares);
+}
+
+/* the pairs' shifts to their frames, and the call's tie statistics */
+static void reg_scatter_shifts(SgRegRun &r, int *shiftx, int *shifty) {
+	for (int k = 0; k < r.pl.npairs_total; k++) {
+		const int fr[2] = {r.pl.hfa[k], r.pl.hfb[k]};
+		for (int h = 0; h < 2; h++) {
+			if (fr[h] < 0)
+				continue;
+			shiftx[fr[h]] = r.hout[k].sx[h];
+			shifty[fr[h]] = r.hout[k].sy[h];
+			if (r.hout[k].amb[h] == 2)
+				r.dv.stats.reg_ties_resolved++;
+			else if (r.hout[k].amb[h])
+				r.dv.stats.reg_ties_unresolved++;
+		}
+	}
+}
+
+/* the end of the call's device span, the quality values, and (normalize_q) their normalisation */
+static int reg_quality_readback(SgRegRun &r, const int *included, double *quality, bool normalize_q) {
+	sg_ctx *ctx = r.ctx;
+	SgDevice &dv = r.dv;
+	const SgRegPlan &pl = r.pl;
+	const std::vector<int> &todo = pl.todo;
+	std::vector<double> qual;
+	if (r.q_launched)	/* the span ends with the quality estimate's stream */
+		HIPCHK(hipStreamWaitEvent(r.s, dv.aux_ev[0], 0));
+	HIPCHK(hipEventRecord(dv.ev[1], r.s));
+	if (int qrc = reg_quality_finish(ctx, dv, (int)pl.qframes.size(), r.q_launched, qual))
+		return qrc;
+	{
+		float ms = 0.f;
+		HIPCHK(hipEventSynchronize(dv.ev[1]));
+		HIPCHK(hipEventElapsedTime(&ms, dv.ev[0], dv.ev[1]));
+		dv.stats.reg_ms = ms;
+	}
+	/* quality: q_min/q_max seeded by the reference frame, then frames in index order with
+	 * the reference's min() macro (src/core/siril.h), then normalizeQualityData */
+	if (!normalize_q) {	/* raw values of the processed frames (sharded registration) */
+		quality[pl.ref_image] = qual[0];
+		for (size_t k = 0; k < todo.size(); k++)
+			quality[todo[k]] = qual[k + 1];
+		return SG_OK;
+	}
+	double q_min = qual[0], q_max = qual[0];
+	quality[pl.ref_image] = qual[0];
+	for (size_t k = 0; k < todo.size(); k++) {
+		const double qv = qual[k + 1];
+		quality[todo[k]] = qv;
+		if (qv > q_max)
+			q_max = qv;
+		q_min = (q_min < qv) ? q_min : qv;
+	}
+	for (int f = 0; f < pl.nframes; f++) {
+		if (included && !included[f])
+			continue;
+		quality[f] -= q_min;
+		quality[f] /= (q_max - q_min);
+	}
+	return SG_OK;
+}
+
+/* tables, LDS limits, workspace and pair table of a planned call, then the quality estimate (or
+ * its deferral) and the reference spectrum */
+static int reg_setup(SgRegRun &r) {
+	sg_ctx *ctx = r.ctx;
+	if (int rc = reg_upload_tables64(r))
+		return rc;
+	HIPCHK(hipEventRecord(r.dv.ev[0], r.s));	/* the call's device span (sg_stack_stats.reg_ms) */
+	reg_raise_lds(r.pl);
+	if (int rc = reg_carve_workspace(r))
+		return rc;
+	if (int rc = reg_upload_tables32(r))
+		return rc;
+	if (int rc = reg_ref_stream(r))
+		return rc;
+	if (int rc = reg_upload_pairs(r))
+		return rc;
+	if (int rc = reg_quality_start(r))
+		return rc;
+	return reg_ref_spectrum(r);
+}
+
 static int reg_dft_device(sg_ctx *ctx, int dev_index, const uint16_t *d_sel_p, int64_t fpitch, int64_t rpitch,
 		int nframes, int S, int ref_image, const int *included, int *shiftx, int *shifty, double *quality, void *stream,
 		bool normalize_q) {
 	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size() || !d_sel_p || !shiftx || !shifty || !quality)
 		return SG_ERR_GENERIC;
-	const SgSel d_sel{d_sel_p, (long long)fpitch, (long long)rpitch};
-	if (nframes < 1)
-		return set_err(ctx, SG_ERR_GENERIC, "no frame to register%s%ld", "", nframes);
-	if (S < 4 || S > 4096)
-		return set_err(ctx, SG_ERR_SIZE, "DFT registration takes selection sides 4 to 4096%s (got %ld)", "", S);
-	if (ref_image < 0)
-		ref_image = 0;	/* seq->reference_image == -1 -> 0 (:212-215) */
-	if (ref_image >= nframes)
-		return set_err(ctx, SG_ERR_GENERIC, "reference image out of range%s %ld", "", ref_image);
+	SgRegPlan pl;
+	if (int rc = sg_reg_plan(nframes, S, ref_image, included, fpitch, rpitch, ctx->knobs, pl))
+		return set_err(ctx, rc, "%s%.0ld", pl.err, 0);
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
-	const int logS = ilog2(S);
-	const size_t plane = (size_t)S * S;
-	/* power-of-two sides take the half-spectrum passes; any other side the generic mixed-radix /
-	 * Bluestein passes (SG_REG_PATH=3 forces those for a power of two, A/B; the round-1/2 full-
-	 * spectrum pass orders 0 / 1 were removed in round 4) */
-	const int path = ctx->knobs.reg_path;	/* A/B knob SG_REG_PATH */
-	const bool generic = (S & (S - 1)) != 0 || S < 8 || path == 3;
-	const bool half = !generic;	/* power of two: the half-spectrum passes */
 	/* the call's tie statistics: the device's record (one host thread per device), published to
 	 * the context when the call returns */
 	dv.stats.reg_ties_resolved = dv.stats.reg_ties_unresolved = dv.stats.reg_fp64_reruns = 0;
@@ -1913,658 +2462,26 @@ static int reg_dft_device(sg_ctx *ctx, int dev_index, const uint16_t *d_sel_p, i
 			c->stats.reg_ms = s.reg_ms;
 		}
 	} publish{ctx, dv.stats};
-
-	/* frames to register, in index order (the reference skips ref and excluded frames) */
-	std::vector<int> todo;
-	for (int f = 0; f < nframes; f++)
-		if (f != ref_image && (!included || included[f]))
-			todo.push_back(f);
-
-	/* tables: twiddles exp(-2 pi i k / S); generic path: its plan, and for Bluestein the
-	 * m-point twiddles, the chirp c_j = exp(-i pi j^2 / S) and FFT_m(b) */
-	SgGenPlan pl;
-	memset(&pl, 0, sizeof pl);
-	SgGenTables tbl;
-	memset(&tbl, 0, sizeof tbl);
-	{
-		const bool blue = generic && !make_plan(S, pl);
-		size_t m = 1;
-		if (blue) {
-			pl.bluestein = 1;
-			pl.m = 1;
-			while (pl.m < 2 * S - 1)
-				pl.m <<= 1;
-			m = pl.m;
-		}
-		/* table layout: tw (4 S), then for Bluestein twm (4 m), the chirp (2 S), bhat (2 m) */
-		const size_t n_tw = 4 * (size_t)S, n_twm = blue ? 4 * m : 0, n_ch = blue ? 2 * (size_t)S : 0;
-		const size_t total = n_tw + n_twm + n_ch + (blue ? 2 * m : 0);
-		/* the tables depend on S (and the path) only: uploaded when either changes */
-		if (dv.reg_tab_S != S || dv.reg_tab_generic != (int)generic) {
-			std::vector<double> tw, twm, ch, bh;
-			make_twiddles(S, tw);
-			if (blue) {
-				make_twiddles((int)m, twm);
-				ch.assign(2 * (size_t)S, 0.0);
-				std::vector<double> br(m, 0.0), bi(m, 0.0);
-				for (int j = 0; j < S; j++) {
-					const long long q = ((long long)j * j) % (2ll * S);	/* j^2 mod 2S keeps the angle exact */
-					const double a = -M_PI * (double)q / (double)S;
-					ch[2 * j] = cos(a);
-					ch[2 * j + 1] = sin(a);
-					br[j] = ch[2 * j];
-					bi[j] = -ch[2 * j + 1];	/* b_j = conj c_j */
-					if (j) {
-						br[m - j] = br[j];
-						bi[m - j] = bi[j];
-					}
-				}
-				host_fft_pow2(br, bi, (int)m);
-				bh.assign(2 * m, 0.0);
-				for (size_t k = 0; k < m; k++) {
-					bh[2 * k] = br[k];
-					bh[2 * k + 1] = bi[k];
-				}
-			}
-			dv.reg_tab_S = 0;
-			HIPCHK(ensure(dv.reg_tw, sizeof(double) * total));
-			double *d = (double *)dv.reg_tw.p;
-			HIPCHK(hipMemcpyAsync(d, tw.data(), sizeof(double) * n_tw, hipMemcpyHostToDevice, s));
-			if (blue) {
-				HIPCHK(hipMemcpyAsync(d + n_tw, twm.data(), sizeof(double) * n_twm, hipMemcpyHostToDevice, s));
-				HIPCHK(hipMemcpyAsync(d + n_tw + n_twm, ch.data(), sizeof(double) * n_ch, hipMemcpyHostToDevice, s));
-				HIPCHK(hipMemcpyAsync(d + n_tw + n_twm + n_ch, bh.data(), sizeof(double) * 2 * m, hipMemcpyHostToDevice, s));
-			}
-			HIPCHK(hipStreamSynchronize(s));	/* the host vectors die here */
-			dv.reg_tab_S = S;
-			dv.reg_tab_generic = (int)generic;
-		}
-		double *d = (double *)dv.reg_tw.p;
-		tbl.tw = (const sg_c64 *)d;
-		if (blue) {
-			tbl.twm = (const sg_c64 *)(d + n_tw);
-			tbl.chirp = (const sg_c64 *)(d + n_tw + n_twm);
-			tbl.bhat = (const sg_c64 *)(d + n_tw + n_twm + n_ch);
-		}
-	}
-	const sg_c64 *tw = tbl.tw;
-
-	HIPCHK(hipEventRecord(dv.ev[0], s));	/* the call's device span (sg_stack_stats.reg_ms) */
-	/* quality of the reference and of every registered frame */
-	std::vector<int> qframes;
-	qframes.push_back(ref_image);
-	qframes.insert(qframes.end(), todo.begin(), todo.end());
-	std::vector<double> qual;
-	bool q_launched = false;
-	int rc = SG_OK;
-
-	/* precision of the main passes: the power-of-two half-spectrum passes run in fp32
-	 * (SG_REG_FP=32, default: half the plane bytes and LDS), and a pair whose correlation
-	 * maximum is a near tie at fp32 tolerance is re-run in fp64 (the arg-max is then exactly
-	 * the fp64 one wherever fp64 is not itself near a tie; those go to the exact integer
-	 * correlations).  The other pass orders and the generic path are fp64. */
-	const bool fp32 = half && ctx->knobs.reg_fp == 32;
-	const size_t esz = fp32 ? sizeof(float2) : sizeof(sg_c64);
-	/* pairs per launch: up to 2 GB of pair planes (32 at S = 2048 on the fp64 half path).
-	 * Half-spectrum passes, configs[1]: 32 or 64 pairs 8.95-9.07 ms, 16: 9.08, 4: 9.22-9.32,
-	 * 2: 9.02-9.15, 1: 9.8 ms of registration (round-2 gpu_regbatch.sh) */
-	const size_t pair_bytes = plane * esz * (generic ? 2 : 1);	/* generic: + transposed plane */
-	int B = (int)((size_t)(2048u << 20) / pair_bytes);
-	if (B < 1)
-		B = 1;
-	if (B > 64)
-		B = 64;
-	if (ctx->knobs.reg_batch > 0)	/* A/B knob SG_REG_BATCH: pairs per launch */
-		B = ctx->knobs.reg_batch;
-	const int npairs_total = (int)(todo.size() + 1) / 2;
-	if (B > npairs_total && npairs_total > 0)
-		B = npairs_total;
-	const int Bc = B > 1 ? B : 1;
-	/* fp64 re-runs of near ties in the same work buffer */
-	const int B64 = fp32 ? (int)std::max<size_t>(1, (size_t)Bc * pair_bytes / (plane * sizeof(sg_c64))) : Bc;
-	const size_t row_lds = (size_t)SG_PADN(S) * sizeof(sg_c64), row_lds32 = (size_t)SG_PADN(S) * sizeof(float2);
-	int CW = 8192 / S;
-	if (CW < 1)
-		CW = 1;
-	if (CW > 8)
-		CW = 8;
-	if (ctx->knobs.reg_cw > 0)	/* A/B knob SG_REG_CW: columns per column-pass workgroup */
-		CW = ctx->knobs.reg_cw;
-	/* threads: 8 elements per thread in every fp64 LDS FFT (sg_stockham_pass's register
-	 * budget), 16 in the fp32 column pass; at least one wave, at most 1024 */
-	auto thr_for = [](int elems) { return elems / 8 < 64 ? 64 : elems / 8; };
-	const int row_thr = thr_for(S);
-	/* half-spectrum columns: a strip stays inside one half (CW divides S/2) */
-	const int CWh = CW < S / 2 ? CW : S / 2;
-	const size_t colh_lds = (size_t)CWh * sg_col_stride<sg_c64>(S) * sizeof(sg_c64);
-	const int colh_thr = thr_for(CWh * S);
-	/* fp32 columns: CW32 columns per strip (8: 64-B row segments), 16 elements per thread */
-	int CW32 = ctx->knobs.reg_cw32;
-	while (CW32 > 1 && (CW32 > S / 2 || CW32 * S > 16 * 1024))
-		CW32 >>= 1;
-	const int ept32 = CW32 * S / 1024 > 8 ? 16 : 8;
-	const int colh_thr32 = std::max(64, CW32 * S / ept32);
-	const size_t colh_lds32 = (size_t)CW32 * sg_col_stride<float2>(S) * sizeof(float2);
-	const int colocc = ctx->knobs.reg_colocc;
-	/* the wave-level fp32 column pass: S = 2048 only (32 x 64 four-step transforms) */
-	const bool wcol = S == 2048 && ctx->knobs.reg_wcol;
-	int rpw = ctx->knobs.reg_rpw;	/* A/B knob SG_REG_RPW: rows per wave of the wave-level forward rows */
-	while (rpw > 1 && (S / 4) % rpw)
-		rpw >>= 1;
-	const size_t wcol_lds = (size_t)4 * SG_WCOL_CS * sizeof(float2);
-	/* rows per forward-row workgroup (the next row prefetched during this one's transform) */
-	int rpb = ctx->knobs.reg_rpb;
-	while (rpb > 1 && S % rpb != 0)
-		rpb >>= 1;
-	const int xcdmap = ctx->knobs.reg_xcd;	/* A/B knob SG_REG_XCD: 0 = strips in dispatch order */
-	/* generic rows: Bluestein needs m/8 threads (sg_lds_fft), the mixed passes ceil(S / 8) (ceil(S / 7)
-	 * with a radix-7 pass) rounded to whole waves (sg_gen_pass_ip's items per thread) */
-	bool has7 = false;
-	for (int q = 0; q < pl.npass; q++)
-		has7 |= pl.radix[q] == 7;
-	const int gen_thr = pl.bluestein ? (pl.m / 8 < 64 ? 64 : pl.m / 8)
-					 : std::max(64, ((has7 ? (S + 6) / 7 : (S + 7) / 8) + 63) / 64 * 64);
-	const size_t gen_lds = pl.bluestein ? (size_t)SG_PADN(pl.m) * sizeof(sg_c64) : row_lds;
-	/* one instantiation per transform kind (register allocation is per kernel) */
-	const void *k_rows = pl.bluestein ? (const void *)k_gen_rows<true> : (const void *)k_gen_rows<false>;
-	/* the fused generic column pass: mixed-radix plans whose two rows fit a block and the LDS
-	 * (SG_REG_GENFUSE=0: the three-kernel sequence, A/B) */
-	const bool gen_fuse = generic && !pl.bluestein && 2 * gen_thr <= 1024 && 2 * gen_lds <= 160 * 1024 &&
-			ctx->knobs.reg_genfuse;
-	if (gen_fuse)
-		(void)hipFuncSetAttribute((const void *)k_gen_cols_xpower, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)(2 * gen_lds));
-	auto gen_rows = [&](dim3 grid, auto... a) {
-		if (pl.bluestein)
-			hipLaunchKernelGGL(k_gen_rows<true>, grid, dim3(gen_thr), gen_lds, s, a...);
-		else
-			hipLaunchKernelGGL(k_gen_rows<false>, grid, dim3(gen_thr), gen_lds, s, a...);
-	};
-	if (!generic) {
-		(void)hipFuncSetAttribute((const void *)k_reg_cols<sg_c64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_fwd_half<sg_c64>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)row_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_inv_half_argmax<sg_c64, false>,
-				hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_inv_half_argmax<sg_c64, true>,
-				hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower<sg_c64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_fwd_half<float2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)row_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_inv_half_argmax<float2, false>,
-				hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols<float2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols<float2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower<float2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower<float2, 8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower<float2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)colh_lds32);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower_w<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)wcol_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower_w<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)(2 * wcol_lds));
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_xpower_w<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)wcol_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_cols_fwd_perm_w, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)wcol_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_fwd_half_w<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)wcol_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_fwd_half_w<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)wcol_lds);
-		(void)hipFuncSetAttribute((const void *)k_reg_rows_inv_half_w, hipFuncAttributeMaxDynamicSharedMemorySize,
-				(int)wcol_lds);
-	} else {
-		(void)hipFuncSetAttribute(k_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds);
-	}
-
-	/* device workspace: reference spectrum (fp64, and fp32 behind it), pair planes, per-row
-	 * partials, then (all pairs of the call, uploaded once / read back once) the pair table,
-	 * the per-pair results, the frames' energies (two sets: the main passes and the near-tie
-	 * re-runs) and the near-tie candidates of one batch */
-	const int NP = npairs_total > 0 ? npairs_total : 1;
-	/* wave-level column pass: the fp32 reference spectrum also in its lane order (k_spec_perm,
-	 * SG_REG_SPECP=0: staged through LDS, A/B) */
-	const bool specp_on = fp32 && wcol && ctx->knobs.reg_specp;
-	HIPCHK(ensure(dv.reg_spec, plane * sizeof(sg_c64) + (fp32 ? plane * sizeof(float2) : 0) +
-			(specp_on ? plane / 2 * sizeof(float2) : 0)));
-	/* the fp64 near-tie re-runs use the same buffer: at least one fp64 plane (B64 >= 1 even
-	 * when the fp32 batch is a single pair, whose plane is half that size) */
-	HIPCHK(ensure(dv.reg_work, std::max((size_t)Bc * pair_bytes, (size_t)B64 * plane * sizeof(sg_c64))));
-	const size_t o_out = ((size_t)std::max(Bc, B64) * S * sizeof(SgBest) + 255) & ~(size_t)255;
-	const size_t o_fab = o_out + (((size_t)(NP + 1) * sizeof(SgRegOut) + 255) & ~(size_t)255);
-	const size_t o_en = o_fab + (((size_t)(NP + 1) * 4 * sizeof(int) + 255) & ~(size_t)255);
-	const size_t o_cand = o_en + (((size_t)nframes * 2 * sizeof(unsigned long long) + 255) & ~(size_t)255);
-	const size_t o_res2 = o_cand + (((size_t)std::max(Bc, B64) * 2 * sizeof(SgCand) + 255) & ~(size_t)255);
-	const size_t ws = o_res2 + (size_t)(NP + 1) * sizeof(SgRegOut);
-	HIPCHK(ensure(dv.reg_best, ws));
-	char *wsp = (char *)dv.reg_best.p;
-	sg_c64 *spec = (sg_c64 *)dv.reg_spec.p, *work = (sg_c64 *)dv.reg_work.p;
-	float2 *spec32 = (float2 *)((char *)dv.reg_spec.p + plane * sizeof(sg_c64)), *work32 = (float2 *)dv.reg_work.p;
-	float2 *specp32 = specp_on ? spec32 + plane : nullptr;
-	sg_c64 *work2 = work + (size_t)Bc * plane;	/* generic path: transposed planes */
-	SgBest *best = (SgBest *)wsp;
-	SgRegOut *d_out = (SgRegOut *)(wsp + o_out), *d_res2 = (SgRegOut *)(wsp + o_res2);
-	int *d_fa = (int *)(wsp + o_fab), *d_fb = d_fa + (NP + 1), *d_fa2 = d_fb + (NP + 1), *d_fb2 = d_fa2 + (NP + 1);
-	unsigned long long *energy = (unsigned long long *)(wsp + o_en), *energy2 = energy + nframes;
-	SgCand *cand = (SgCand *)(wsp + o_cand);
-	HIPCHK(hipMemsetAsync(energy, 0, sizeof(unsigned long long) * 2 * nframes, s));
-	/* fp32 twiddles, rounded from the fp64 table (behind the fp64 tables in reg_tw) */
-	const float2 *tw32 = nullptr;
-	if (fp32) {
-		if (dv.reg_tw32_S != S) {
-			dv.reg_tw32_S = 0;
-			HIPCHK(ensure(dv.reg_tw32, 2 * (size_t)S * sizeof(float2)));
-			std::vector<double> t64;
-			make_twiddles(S, t64);
-			std::vector<float> t32(t64.size());
-			for (size_t i = 0; i < t64.size(); i++)
-				t32[i] = (float)t64[i];
-			HIPCHK(hipMemcpyAsync(dv.reg_tw32.p, t32.data(), sizeof(float) * t32.size(), hipMemcpyHostToDevice, s));
-			HIPCHK(hipStreamSynchronize(s));
-			dv.reg_tw32_S = S;
-		}
-		tw32 = (const float2 *)dv.reg_tw32.p;
-	}
-
-	const bool ref_conc = fp32 && ctx->knobs.reg_refconc;	/* A/B knob SG_REG_REFCONC */
-	/* SG_REG_QFOLD (A/B): the quality estimate's subsample from the wave-level forward rows (every
-	 * frame of qframes passes through them: the reference and each pair), then only the gradient
-	 * kernel on the aux stream behind the last batch's forward rows */
-	const int qfold = (specp32 && npairs_total > 0 && S == 2048) ? ctx->knobs.reg_qfold : 0;
-	SgQBufs qfb{};
-	int q_qbase = 0;
-	bool q_fold_last = false;
-	auto fwd_w_launch = [&](hipStream_t st, const int *fa, const int *fb, int np, float2 *out, unsigned long long *en,
-			int rows, int qbase) {
-		if (qfold) {
-			const int waves = (S + qfold - 1) / qfold;
-			hipLaunchKernelGGL(k_reg_rows_fwd_half_w<true>, dim3((waves + 3) / 4, np), dim3(256), wcol_lds, st, d_sel, fa,
-					fb, tw32, out, en, qfold, qfb.qbuf, qfb.qmax, qbase);
-		} else {
-			hipLaunchKernelGGL(k_reg_rows_fwd_half_w<false>, dim3(S / 4 / rows, np), dim3(256), wcol_lds, st, d_sel, fa,
-					fb, tw32, out, en, rows, (uint16_t *)nullptr, (unsigned int *)nullptr, 0);
-		}
-	};
-	bool ref_pending = false, q_deferred = false;
-	if (ref_conc && !dv.aux2) {
-		HIPCHK(hipStreamCreateWithFlags(&dv.aux2, hipStreamNonBlocking));
-		for (int k = 0; k < 2; k++)
-			HIPCHK(hipEventCreateWithFlags(&dv.aux2_ev[k], hipEventDisableTiming));
-	}
-
-	/* pair k = frames todo[2k], todo[2k+1] (-1: odd count, imaginary part zero); slot NP is
-	 * the reference spectrum's (ref_image, -1) */
-	std::vector<int> hfa(NP + 1), hfb(NP + 1);
-	std::vector<SgRegOut> hout((size_t)NP);
-	for (int k = 0; k < npairs_total; k++) {
-		hfa[k] = todo[2 * k];
-		hfb[k] = (2 * (size_t)k + 1 < todo.size()) ? todo[2 * k + 1] : -1;
-	}
-	hfa[NP] = ref_image;
-	hfb[NP] = -1;
-	/* the pair table goes up, and the results come back, through a pinned block (the previous
-	 * call's copies are done: every call ends on a stream synchronize) */
-	const size_t pin_res = ((size_t)2 * (NP + 1) * sizeof(int) + 63) & ~(size_t)63;
-	const size_t pin_bytes = pin_res + (size_t)NP * sizeof(SgRegOut);
-	if (dv.reg_pin_n < pin_bytes) {
-		if (dv.reg_pin)
-			(void)hipHostFree(dv.reg_pin);
-		dv.reg_pin = nullptr;
-		dv.reg_pin_n = 0;
-		HIPCHK(hipHostMalloc(&dv.reg_pin, pin_bytes));
-		dv.reg_pin_n = pin_bytes;
-	}
-	int *pfab = (int *)dv.reg_pin;
-	SgRegOut *pout = (SgRegOut *)((char *)dv.reg_pin + pin_res);
-	memcpy(pfab, hfa.data(), sizeof(int) * (NP + 1));
-	memcpy(pfab + (NP + 1), hfb.data(), sizeof(int) * (NP + 1));
-	HIPCHK(hipMemcpyAsync(d_fa, pfab, sizeof(int) * 2 * (NP + 1), hipMemcpyHostToDevice, s));	/* d_fb = d_fa + NP + 1 */
-
-	const dim3 tgrid((S + 31) / 32, (S + 31) / 32);
-	/* generic passes up to the cross power's inverse: transposed spectrum of the rows of `fa`
-	 * / `fb` pairs -> `work` holds the pairs' inverse column transforms in row layout */
-	auto gen_forward = [&](const int *fa, const int *fb, int np, unsigned long long *en) -> int {
-		gen_rows(dim3(S, np), d_sel, fa, fb, work, S, pl, tbl,
-				(int)SG_GEN_FWD_U16, 0, en, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL(k_gen_transpose, dim3(tgrid.x, tgrid.y, np), dim3(32, 8), 0, s, (const sg_c64 *)work, work2, S);
-		HIPCHK(hipGetLastError());
-		if (gen_fuse) {	/* forward columns + cross power + inverse columns in one pass */
-			hipLaunchKernelGGL(k_gen_cols_xpower, dim3(S / 2 + 1, np), dim3(2 * gen_thr), 2 * gen_lds, s, work2,
-					(const sg_c64 *)spec, S, pl, tw);
-			HIPCHK(hipGetLastError());
-		} else {
-			gen_rows(dim3(S, np), d_sel, fa, fb, work2, S, pl, tbl,
-					(int)SG_GEN_C2C, 0, en, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL(k_gen_xpower, dim3(1024, np), dim3(256), 0, s, work2, (const sg_c64 *)spec, S);
-			HIPCHK(hipGetLastError());
-			gen_rows(dim3(S, np), d_sel, fa, fb, work2, S, pl, tbl,
-					(int)SG_GEN_C2C, 1, en, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-			HIPCHK(hipGetLastError());
-		}
-		hipLaunchKernelGGL(k_gen_transpose, dim3(tgrid.x, tgrid.y, np), dim3(32, 8), 0, s, (const sg_c64 *)work2, work, S);
-		HIPCHK(hipGetLastError());
-		return SG_OK;
-	};
-	/* half-spectrum passes of the pairs (fa, fb)[0, np): the reference spectrum (spec) of the
-	 * precision (fp64 or fp32), `mode` 0 = top-2 arg-max into best, 1 = near-tie candidates */
-	auto half_spec64 = [&]() -> int {
-		hipLaunchKernelGGL(k_reg_rows_fwd_half<sg_c64>, dim3(S / rpb, 1), dim3(row_thr), row_lds, s, d_sel, d_fa + NP,
-				d_fb + NP, S, tw, spec, energy2, rpb);
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL((k_reg_cols<sg_c64, 8>), dim3(S / 2 / CWh, 1), dim3(colh_thr), colh_lds, s, spec, S, logS,
-				CWh, tw, 0, xcdmap);
-		HIPCHK(hipGetLastError());
-		return SG_OK;
-	};
-	auto half64 = [&](const int *fa, const int *fb, int np, unsigned long long *en, int mode, const SgRegOut *res)
-			-> int {
-		hipLaunchKernelGGL(k_reg_rows_fwd_half<sg_c64>, dim3(S / rpb, np), dim3(row_thr), row_lds, s, d_sel, fa, fb, S, tw,
-				work, en, rpb);
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL((k_reg_cols_xpower<sg_c64, 8>), dim3(S / CWh, np), dim3(colh_thr), colh_lds, s, work,
-				(const sg_c64 *)spec, S, CWh, tw, xcdmap, ctx->knobs.reg_pb);
-		HIPCHK(hipGetLastError());
-		if (mode)
-			hipLaunchKernelGGL((k_reg_rows_inv_half_argmax<sg_c64, true>), dim3(S, np), dim3(row_thr), row_lds, s,
-					(const sg_c64 *)work, S, tw, best, res, cand);
-		else
-			hipLaunchKernelGGL((k_reg_rows_inv_half_argmax<sg_c64, false>), dim3(S, np), dim3(row_thr), row_lds, s,
-					(const sg_c64 *)work, S, tw, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-		HIPCHK(hipGetLastError());
-		return SG_OK;
-	};
-	auto half32 = [&](const int *fa, const int *fb, int np, unsigned long long *en) -> int {
-		if (wcol)
-			fwd_w_launch(s, fa, fb, np, work32, en, rpw, q_qbase);
-		else
-			hipLaunchKernelGGL(k_reg_rows_fwd_half<float2>, dim3(S / rpb, np), dim3(row_thr), row_lds32, s, d_sel, fa,
-					fb, S, tw32, work32, en, rpb);
-		HIPCHK(hipGetLastError());
-		if (q_deferred) {	/* SG_REG_QAFTER: the quality estimate beside the column pass instead */
-			q_deferred = false;
-			if (int r = reg_quality_launch(ctx, dv, s, d_sel, S, qframes, &q_launched))
-				return r;
-		}
-		if (ref_pending) {	/* the reference spectrum, from its stream */
-			HIPCHK(hipStreamWaitEvent(s, dv.aux2_ev[1], 0));
-			ref_pending = false;
-		}
-		if (qfold && q_fold_last) {	/* every frame subsampled (the reference's rows waited for above) */
-			const int nq = (int)qframes.size(), xs = (S - 1) / 3;
-			HIPCHK(hipEventRecord(dv.aux_ev[1], s));
-			HIPCHK(hipStreamWaitEvent(dv.aux, dv.aux_ev[1], 0));
-			if (int r = reg_quality_grad(ctx, dv, nq, xs, xs, qfb))
-				return r;
-			q_launched = true;
-		}
-		if (wcol && specp32 && ctx->knobs.reg_wcolw == 8)	/* 8-column strips: 64-B row segments, one workgroup per CU */
-			hipLaunchKernelGGL((k_reg_cols_xpower_w<true, 8>), dim3(S / 8, np), dim3(512), 2 * wcol_lds, s, work32,
-					(const float2 *)spec32, (const float2 *)specp32, tw32, xcdmap);
-		else if (wcol && specp32)	/* S = 2048: the wave-level column pass (SG_REG_WCOL=0: the block-level one, A/B) */
-			hipLaunchKernelGGL((k_reg_cols_xpower_w<true, 4>), dim3(S / 4, np), dim3(256), wcol_lds, s, work32,
-					(const float2 *)spec32, (const float2 *)specp32, tw32, xcdmap);
-		else if (wcol)
-			hipLaunchKernelGGL((k_reg_cols_xpower_w<false, 4>), dim3(S / 4, np), dim3(256), wcol_lds, s, work32,
-					(const float2 *)spec32, (const float2 *)nullptr, tw32, xcdmap);
-		else if (ept32 == 16)
-			hipLaunchKernelGGL((k_reg_cols_xpower<float2, 16>), dim3(S / CW32, np), dim3(colh_thr32), colh_lds32, s,
-					work32, (const float2 *)spec32, S, CW32, tw32, xcdmap, 1);
-		else if (colocc)	/* default (SG_REG_COLOCC=1): 64 VGPRs (8 waves / SIMD, two 1024-thread workgroups per CU) */
-			hipLaunchKernelGGL((k_reg_cols_xpower<float2, 8, 8>), dim3(S / CW32, np), dim3(colh_thr32), colh_lds32, s,
-					work32, (const float2 *)spec32, S, CW32, tw32, xcdmap, 1);
-		else
-			hipLaunchKernelGGL((k_reg_cols_xpower<float2, 8>), dim3(S / CW32, np), dim3(colh_thr32), colh_lds32, s,
-					work32, (const float2 *)spec32, S, CW32, tw32, xcdmap, 1);
-		HIPCHK(hipGetLastError());
-		if (wcol)
-			hipLaunchKernelGGL(k_reg_rows_inv_half_w, dim3(S / 4, np), dim3(256), wcol_lds, s, (const float2 *)work32,
-					tw32, best);
-		else
-			hipLaunchKernelGGL((k_reg_rows_inv_half_argmax<float2, false>), dim3(S, np), dim3(row_thr), row_lds32, s,
-					(const float2 *)work32, S, tw32, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-		HIPCHK(hipGetLastError());
-		return SG_OK;
-	};
-
-	/* the quality estimate on the aux stream, queued behind the main stream's table uploads and
-	 * fills (queued ahead of them, its long-running workgroups held the fills' single workgroup
-	 * back 0.2 ms, profiles/r05m_*) */
-	if (qfold) {	/* the sums zeroed on the call's stream, ahead of every forward row launch */
-		const int nq = (int)qframes.size(), xs = (S - 1) / 3;
-		if (int r = reg_quality_buffers(ctx, dv, nq, xs, xs, qfb))
-			return r;
-		HIPCHK(hipMemsetAsync(qfb.acc, 0, (size_t)nq * (3 * sizeof(unsigned long long) + sizeof(unsigned int)), s));
-	} else if (fp32 && npairs_total > 0 && ctx->knobs.reg_qafter) {
-		q_deferred = true;
-	} else {
-		rc = reg_quality_launch(ctx, dv, s, d_sel, S, qframes, &q_launched);
-		if (rc)
-			return rc;
-	}
-
-	/* reference spectrum R = FFT2(ref) (half layout: the A' half only; generic: transposed) */
-	if (generic) {
-		gen_rows(dim3(S, 1), d_sel, d_fa + NP, d_fb + NP, work, S, pl,
-				tbl, (int)SG_GEN_FWD_U16, 0, energy, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL(k_gen_transpose, dim3(tgrid.x, tgrid.y, 1), dim3(32, 8), 0, s, (const sg_c64 *)work, spec, S);
-		HIPCHK(hipGetLastError());
-		gen_rows(dim3(S, 1), d_sel, d_fa + NP, d_fb + NP, spec, S, pl,
-				tbl, (int)SG_GEN_C2C, 0, energy, best, (const SgRegOut *)nullptr, (SgCand *)nullptr);
-	} else if (fp32) {
-		/* the reference spectrum on its own stream beside the first batch's forward rows (which do
-		 * not read it; the batch's column pass waits for it).  One workgroup per CU at most: run
-		 * alone it is 0.27 ms of latency-bound passes ahead of every pair (profiles/r05l_*) */
-		hipStream_t rs = s;
-		if (ref_conc) {
-			HIPCHK(hipEventRecord(dv.aux2_ev[0], s));
-			HIPCHK(hipStreamWaitEvent(dv.aux2, dv.aux2_ev[0], 0));
-			rs = dv.aux2;
-		}
-		if (specp32) {	/* wave-level passes: one row per wave, the columns straight into lane order */
-			fwd_w_launch(rs, d_fa + NP, d_fb + NP, 1, spec32, energy, 1, 0);
-			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL(k_reg_cols_fwd_perm_w, dim3(S / 2 / 4), dim3(256), wcol_lds, rs, spec32, specp32, tw32);
-		} else {
-			hipLaunchKernelGGL(k_reg_rows_fwd_half<float2>, dim3(S / rpb, 1), dim3(row_thr), row_lds32, rs, d_sel,
-					d_fa + NP, d_fb + NP, S, tw32, spec32, energy, rpb);
-			HIPCHK(hipGetLastError());
-			if (ept32 == 16)
-				hipLaunchKernelGGL((k_reg_cols<float2, 16>), dim3(S / 2 / CW32, 1), dim3(colh_thr32), colh_lds32, rs,
-						spec32, S, logS, CW32, tw32, 0, xcdmap);
-			else
-				hipLaunchKernelGGL((k_reg_cols<float2, 8>), dim3(S / 2 / CW32, 1), dim3(colh_thr32), colh_lds32, rs,
-						spec32, S, logS, CW32, tw32, 0, xcdmap);
-		}
-		if (ref_conc) {
-			HIPCHK(hipGetLastError());
-			HIPCHK(hipEventRecord(dv.aux2_ev[1], dv.aux2));
-			ref_pending = true;
-		}
-	} else {
-		hipLaunchKernelGGL(k_reg_rows_fwd_half<sg_c64>, dim3(S / rpb, 1), dim3(row_thr), row_lds, s, d_sel, d_fa + NP,
-				d_fb + NP, S, tw, spec, energy, rpb);
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL((k_reg_cols<sg_c64, 8>), dim3(S / 2 / CWh, 1), dim3(colh_thr), colh_lds, s, spec, S, logS,
-				CWh, tw, 0, xcdmap);
-	}
-	HIPCHK(hipGetLastError());
-	shiftx[ref_image] = 0;
-	shifty[ref_image] = 0;
-	const int tol_main = fp32 ? -15 : -32;
-	for (int p0 = 0; p0 < npairs_total; p0 += B) {
-		const int np = npairs_total - p0 < B ? npairs_total - p0 : B;
-		int count = S;	/* row partials per pair */
-		if (generic) {
-			if (int r = gen_forward(d_fa + p0, d_fb + p0, np, energy))
-				return r;
-			gen_rows(dim3(S, np), d_sel, d_fa + p0, d_fb + p0, work, S,
-					pl, tbl, (int)SG_GEN_INV_ARGMAX, 1, energy, best, (const SgRegOut *)nullptr,
-					(SgCand *)nullptr);
-		} else if (fp32) {
-			q_qbase = 1 + 2 * p0;	/* qframes = ref, todo...: pair k's frames are entries 1 + 2k, 2 + 2k */
-			q_fold_last = p0 + np >= npairs_total;
-			if (int r = half32(d_fa + p0, d_fb + p0, np, energy))
-				return r;
-		} else {
-			if (int r = half64(d_fa + p0, d_fb + p0, np, energy, 0, nullptr))
-				return r;
-		}
-		HIPCHK(hipGetLastError());
-		hipLaunchKernelGGL(k_reg_final, dim3(np), dim3(256), 0, s, (const SgBest *)best, S, count,
-				(const int *)d_fa + p0, (const int *)d_fb + p0, ref_image, (const unsigned long long *)energy, tol_main,
-				d_out + p0);
-		HIPCHK(hipGetLastError());
-	}
-	if (ref_pending) {
-		HIPCHK(hipStreamWaitEvent(s, dv.aux2_ev[1], 0));
-		ref_pending = false;
-	}
-	if (npairs_total > 0)
-		HIPCHK(hipMemcpyAsync(pout, d_out, sizeof(SgRegOut) * npairs_total, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	if (npairs_total > 0)
-		memcpy(hout.data(), pout, sizeof(SgRegOut) * npairs_total);
-
-	/* near ties (the runner-up within the tolerance of the maximum): re-run those pairs.  After
-	 * fp32 passes, first in fp64 (a fresh arg-max at the fp64 tolerance); what is still a near
-	 * tie then lists every index within the tolerance, computes their exact integer
-	 * correlations and takes the largest (lowest index among exact equals) */
-	auto ambiguous = [&](std::vector<int> &amb) {
-		amb.clear();
-		for (int k = 0; k < npairs_total; k++)
-			if (hout[k].amb[0] == 1 || hout[k].amb[1] == 1)
-				amb.push_back(k);
-	};
-	auto upload_subset = [&](const std::vector<int> &amb, std::vector<SgRegOut> &ares) -> int {
-		const int na = (int)amb.size();
-		std::vector<int> afa(na), afb(na);
-		ares.resize(na);
-		for (int i = 0; i < na; i++) {
-			afa[i] = hfa[amb[i]];
-			afb[i] = hfb[amb[i]];
-			ares[i] = hout[amb[i]];
-		}
-		HIPCHK(hipMemcpyAsync(d_fa2, afa.data(), sizeof(int) * na, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(d_fb2, afb.data(), sizeof(int) * na, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(d_res2, ares.data(), sizeof(SgRegOut) * na, hipMemcpyHostToDevice, s));
-		HIPCHK(hipStreamSynchronize(s));	/* the host vectors die here */
-		return SG_OK;
-	};
+	SgRegRun r{ctx, dv, stream ? (hipStream_t)stream : dv.stream, pl, SgSel{d_sel_p, (long long)pl.fpitch, (long long)pl.rpitch}};
+	if (int rc = reg_setup(r))
+		return rc;
+	shiftx[pl.ref_image] = 0;
+	shifty[pl.ref_image] = 0;
+	if (int rc = reg_main_batches(r))
+		return rc;
+	/* near ties: re-run those pairs.  After fp32 passes, first in fp64; what is still a near tie
+	 * then goes to the exact integer correlations */
 	std::vector<int> amb;
 	std::vector<SgRegOut> ares;
-	ambiguous(amb);
-	if (!amb.empty() && fp32) {
-		/* fp64 re-run: the fp64 reference spectrum, then the pairs' fp64 passes and arg-max */
-		if (int r = upload_subset(amb, ares))
-			return r;
-		if (int r = half_spec64())
-			return r;
-		const int na = (int)amb.size();
-		for (int p0 = 0; p0 < na; p0 += B64) {
-			const int np = na - p0 < B64 ? na - p0 : B64;
-			if (int r = half64(d_fa2 + p0, d_fb2 + p0, np, energy2, 0, nullptr))
-				return r;
-			hipLaunchKernelGGL(k_reg_final, dim3(np), dim3(256), 0, s, (const SgBest *)best, S, S,
-					(const int *)d_fa2 + p0, (const int *)d_fb2 + p0, ref_image, (const unsigned long long *)energy,
-					-32, d_res2 + p0);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipMemcpyAsync(ares.data(), d_res2, sizeof(SgRegOut) * na, hipMemcpyDeviceToHost, s));
-		HIPCHK(hipStreamSynchronize(s));
-		for (int i = 0; i < na; i++)
-			hout[amb[i]] = ares[i];
-		dv.stats.reg_fp64_reruns += (uint64_t)na;
-		ambiguous(amb);
-	}
-	if (!amb.empty()) {
-		if (int r = upload_subset(amb, ares))
-			return r;
-		const int na = (int)amb.size();
-		for (int p0 = 0; p0 < na; p0 += B64) {
-			const int np = na - p0 < B64 ? na - p0 : B64;
-			HIPCHK(hipMemsetAsync(cand, 0, sizeof(SgCand) * 2 * np, s));
-			if (generic) {
-				if (int r = gen_forward(d_fa2 + p0, d_fb2 + p0, np, energy2))
-					return r;
-				gen_rows(dim3(S, np), d_sel, d_fa2 + p0, d_fb2 + p0,
-						work, S, pl, tbl, (int)SG_GEN_INV_CAND, 1, energy2, best, (const SgRegOut *)(d_res2 + p0),
-						cand);
-			} else {
-				/* the fp64 spectrum exists on the fp64 half path, and after the fp64 re-run */
-				if (int r = half64(d_fa2 + p0, d_fb2 + p0, np, energy2, 1, (const SgRegOut *)(d_res2 + p0)))
-					return r;
-			}
-			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL(k_reg_exact, dim3(SG_CAND_CAP, 2 * np), dim3(256), 0, s, d_sel, (const int *)d_fa2 + p0,
-					(const int *)d_fb2 + p0, ref_image, S, cand);
-			HIPCHK(hipGetLastError());
-			hipLaunchKernelGGL(k_reg_resolve, dim3((np + 63) / 64), dim3(64), 0, s, (const SgCand *)cand, S, np,
-					d_res2 + p0);
-			HIPCHK(hipGetLastError());
-		}
-		HIPCHK(hipMemcpyAsync(ares.data(), d_res2, sizeof(SgRegOut) * na, hipMemcpyDeviceToHost, s));
-		HIPCHK(hipStreamSynchronize(s));
-		for (int i = 0; i < na; i++)
-			hout[amb[i]] = ares[i];
-	}
-	for (int k = 0; k < npairs_total; k++) {
-		const int fr[2] = {hfa[k], hfb[k]};
-		for (int h = 0; h < 2; h++) {
-			if (fr[h] < 0)
-				continue;
-			shiftx[fr[h]] = hout[k].sx[h];
-			shifty[fr[h]] = hout[k].sy[h];
-			if (hout[k].amb[h] == 2)
-				dv.stats.reg_ties_resolved++;
-			else if (hout[k].amb[h])
-				dv.stats.reg_ties_unresolved++;
-		}
-	}
-
-	if (q_launched)	/* the span ends with the quality estimate's stream */
-		HIPCHK(hipStreamWaitEvent(s, dv.aux_ev[0], 0));
-	HIPCHK(hipEventRecord(dv.ev[1], s));
-	if (int qrc = reg_quality_finish(ctx, dv, (int)qframes.size(), q_launched, qual))
-		return qrc;
-	{
-		float ms = 0.f;
-		HIPCHK(hipEventSynchronize(dv.ev[1]));
-		HIPCHK(hipEventElapsedTime(&ms, dv.ev[0], dv.ev[1]));
-		dv.stats.reg_ms = ms;
-	}
-	/* quality: q_min/q_max seeded by the reference frame, then frames in index order with
-	 * the reference's min() macro (src/core/siril.h), then normalizeQualityData */
-	if (!normalize_q) {	/* raw values of the processed frames (sharded registration) */
-		quality[ref_image] = qual[0];
-		for (size_t k = 0; k < todo.size(); k++)
-			quality[todo[k]] = qual[k + 1];
-		return SG_OK;
-	}
-	double q_min = qual[0], q_max = qual[0];
-	quality[ref_image] = qual[0];
-	for (size_t k = 0; k < todo.size(); k++) {
-		const double qv = qual[k + 1];
-		quality[todo[k]] = qv;
-		if (qv > q_max)
-			q_max = qv;
-		q_min = (q_min < qv) ? q_min : qv;
-	}
-	for (int f = 0; f < nframes; f++) {
-		if (included && !included[f])
-			continue;
-		quality[f] -= q_min;
-		quality[f] /= (q_max - q_min);
-	}
-	return SG_OK;
+	reg_ambiguous(r, amb);
+	if (!amb.empty() && pl.fp32)
+		if (int rc = reg_rerun_fp64(r, amb, ares))
+			return rc;
+	if (!amb.empty())
+		if (int rc = reg_resolve_exact(r, amb, ares))
+			return rc;
+	reg_scatter_shifts(r, shiftx, shifty);
+	return reg_quality_readback(r, included, quality, normalize_q);
 }
 
 /*

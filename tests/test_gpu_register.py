@@ -395,3 +395,69 @@ def test_register_quality_fold_matches(gpu_ctx, rpw):
     for f in (2, 3, 5):
         sel = np.ascontiguousarray(frames[f, y0:y0 + S, x0:x0 + S])
         assert _same_q(np.array([got[2][f]]), np.array([orc.quality(sel)])), (f, got[2][f])
+
+
+# ---- the launch-order knobs: each steers when the quality estimate is queued, when the reference
+# spectrum's stream is waited for, or which instance of a pass runs; none may change a result ----
+
+def _order_case(S, seed):
+    """seven frames, the reference at index 2 and frame 4 excluded: five frames to register, so
+    the third pair has no second frame"""
+    sel = orc.synth(7, 1, S, S, seed=seed, maxshift=min(9, S // 4))[:, 0].copy()
+    sel[:, S // 3:S // 3 + 6, S // 2:S // 2 + 6] = 52000     # structure above the quality threshold
+    inc = np.ones(7, np.int32)
+    inc[4] = 0
+    return sel, inc
+
+
+def _register_under(env, sel, inc):
+    os.environ.update(env)
+    try:
+        with sg.Context() as c:
+            return c.register_dft(sel, ref_image=2, included=inc)
+    finally:
+        for k in env:
+            del os.environ[k]
+
+
+def _assert_same_registration(got, want):
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), (got, want)
+    assert _same_q(got[2], want[2]), (got[2], want[2])
+
+
+@pytest.fixture(scope="module")
+def order_2048(gpu_ctx):
+    sel, inc = _order_case(2048, 171)
+    return sel, inc, gpu_ctx.register_dft(sel, ref_image=2, included=inc)
+
+
+@pytest.mark.parametrize("env", [
+    {"SG_REG_BATCH": "1"},
+    {"SG_REG_BATCH": "2"},      # two batches: the folded subsample's base advances, the gradient follows the last
+    {"SG_REG_QFOLD": "0", "SG_REG_QAFTER": "1"},
+    {"SG_REG_REFCONC": "0"},
+    {"SG_REG_SPECP": "0"},
+    {"SG_REG_WCOLW": "4"},
+    {"SG_REG_WCOL": "0", "SG_REG_CW32": "8"},   # the block-level column pass with 16 elements per thread
+], ids=lambda e: ",".join("%s=%s" % (k[7:], v) for k, v in e.items()))
+def test_register_launch_order_knobs_2048(order_2048, env):
+    """S = 2048 (the smallest side with the wave-level and folded routes): a context opened under
+    each launch-order knob gives the default context's shifts and qualities"""
+    sel, inc, want = order_2048
+    _assert_same_registration(_register_under(env, sel, inc), want)
+
+
+def test_register_launch_order_knobs_256(gpu_ctx):
+    """S = 256 (the smallest side at which a block-level strip is 4 columns of whole waves): the
+    column pass without the 64-VGPR bound, and one pair per batch over five frames to register"""
+    sel, inc = _order_case(256, 172)
+    want = gpu_ctx.register_dft(sel, ref_image=2, included=inc)
+    for env in ({"SG_REG_COLOCC": "0"}, {"SG_REG_BATCH": "1"}):
+        _assert_same_registration(_register_under(env, sel, inc), want)
+
+
+def test_register_launch_order_generic_batches(gpu_ctx):
+    """S = 60: the generic route in three batches of one pair"""
+    sel, inc = _order_case(60, 173)
+    want = gpu_ctx.register_dft(sel, ref_image=2, included=inc)
+    _assert_same_registration(_register_under({"SG_REG_BATCH": "1"}, sel, inc), want)
