@@ -1,8 +1,11 @@
-"""Edge cases of the pixel-pair reduce kernel (k_stack_reduce2: SUM / MAX / MIN / MEAN
+"""Edge cases of the per-lane pixel-pair loop of the reduce kernels (sg_reduce_pairs, which
+k_stack_reduce3's edge segments and k_stack_reduce2 share: SUM / MAX / MIN / MEAN
 NO_REJEC, src/stacking/stacking.c:196-355, 824-1128, 1786-1794) and of the half-spectrum
 registration passes (register_shift_dft, src/registration/registration.c:182-400).
 
-Reduce: odd and tiny widths, shifts that move one pixel of a lane's pair out of the image
+Reduce (every image here is too narrow for an interior segment of k_stack_reduce3, the default
+kernel, so all of it runs the edge loop; tests/test_gpu_reduce_interior.py has the interior
+body): odd and tiny widths, shifts that move one pixel of a lane's pair out of the image
 (nx = -1, nx + 1 = W), shifts larger than the image, rows shifted out of the frame, source
 pixel 0 (`ii > 0`, :307), normalisation of y-shifted zero rows; each case is compared with
 the oracle and with the one-pixel-per-lane kernel (SG_REDUCE1=1), bit for bit.
