@@ -48,6 +48,8 @@ __global__ void k_stack_reduce2(SgStackParams p);
 template <int M, int SEG>
 __global__ void k_stack_reduce3(SgStackParams p, const int *tab, const int *shifty);
 __global__ void k_sum_finalize(SgStackParams p);
+__global__ void k_stack_reduce_wide(SgStackParams p);
+__global__ void k_sum_finalize_wide(SgStackParams p);
 __global__ void k_stack_literal(SgStackParams p, SgChainTables t, unsigned int count, uint8_t *scratch, int phase);
 __global__ void k_synth_fill(uint16_t *frames, int first_frame, int nframes, int C, int H, int W, int row_begin,
 		int row_end, uint64_t seed, int maxshift, int64_t frame_stride, int64_t plane_stride);
@@ -302,7 +304,8 @@ enum SgFlagWord {
 	SG_FL_LOOP_FAULT = 4,	/* a SIGMEDIAN pixel's reference loop never ends */
 	SG_FL_EXPORT = 6,	/* exported WINSORIZED columns */
 	SG_FL_VERDICT = 7,	/* k_norm_fma_check's load verdict */
-	SG_FL_SUM_MAX = 16	/* SUM maximum (byte 64: kept across the bands of a streamed SUM) */
+	SG_FL_SUM_MAX = 16	/* SUM maximum, words 16 and 17 as one little-endian 64-bit value (byte 64: kept across
+				 * the bands of a streamed SUM); the uint32_t kernels write word 16 alone, 17 stays 0 */
 };
 static unsigned int *flag_words(void *ctr_block) {
 	return (unsigned int *)((char *)ctr_block + SG_CTR_REJB);
@@ -351,7 +354,7 @@ static int stack_fold(sg_ctx *ctx, SgDevice &dv, int slot, uint64_t rej[3][2], u
 		}
 	}
 	if (maxim_out)
-		*maxim_out = dv.pend_sum_read[slot] ? fl[SG_FL_SUM_MAX] : 0;
+		*maxim_out = dv.pend_sum_read[slot] ? (uint64_t)fl[SG_FL_SUM_MAX] | (uint64_t)fl[SG_FL_SUM_MAX + 1] << 32 : 0;
 	return SG_OK;
 }
 
@@ -418,7 +421,7 @@ static int prepare_counters(StackCall &c, const SgStackPlan &pl, int sum_mode) {
 	if (!dv.ctr_clean[c.slot])
 		HIPCHK(hipMemsetAsync(cblk, 0, clear_max ? SG_CTRB : SG_CTR_REJB + SG_FL_SUM_MAX * sizeof(unsigned int), c.s));
 	else if (clear_max && pl.sum)
-		HIPCHK(hipMemsetAsync(c.fl + SG_FL_SUM_MAX, 0, sizeof(unsigned int), c.s));
+		HIPCHK(hipMemsetAsync(c.fl + SG_FL_SUM_MAX, 0, 2 * sizeof(unsigned int), c.s));
 	dv.ctr_clean[c.slot] = false;
 	c.p.rej = (unsigned long long *)cblk;
 	c.p.flag_count = c.fl + SG_FL_SLOW;
@@ -669,12 +672,14 @@ static int launch_reduce(StackCall &c, const SgStackPlan &pl, int sum_mode, sg_s
 	SgDevice &dv = *c.dv;
 	SgStackParams &p = c.p;
 	if (pl.sum) {
-		HIPCHK(ensure(dv.sum_buf, sizeof(uint32_t) * pl.npix_img));
+		HIPCHK(ensure(dv.sum_buf, (pl.wide ? sizeof(unsigned long long) : sizeof(uint32_t)) * pl.npix_img));
 		p.sum_buf = (uint32_t *)dv.sum_buf.p;
 	}
 	const dim3 grid(pl.main_grid[0], pl.main_grid[1], pl.main_grid[2]);
 	HIPCHK(hipEventRecord(dv.cev[c.slot][0], c.s));
-	if (pl.main == SG_MAIN_REDUCE3) {
+	if (pl.main == SG_MAIN_REDUCE_WIDE) {
+		hipLaunchKernelGGL(k_stack_reduce_wide, grid, dim3(pl.main_threads), 0, c.s, p);
+	} else if (pl.main == SG_MAIN_REDUCE3) {
 		const int g = log2_index(pl.seg, 3);
 		if (g < 0 || pl.m < 0 || pl.m > 4)
 			return set_err(ctx, SG_ERR_GENERIC, "no reduce kernel for this case%s%.0ld", "", 0);
@@ -697,7 +702,7 @@ static int launch_reduce(StackCall &c, const SgStackPlan &pl, int sum_mode, sg_s
 			pf.row_end = pl.H;
 			gf.y = pl.H;
 		}
-		hipLaunchKernelGGL(k_sum_finalize, gf, dim3(256), 0, c.s, pf);
+		hipLaunchKernelGGL(pl.wide ? k_sum_finalize_wide : k_sum_finalize, gf, dim3(256), 0, c.s, pf);
 		HIPCHK(hipGetLastError());
 		st.launches++;
 	}
@@ -865,11 +870,11 @@ extern "C" int sg_stack_collect(sg_ctx *ctx, int dev_index, uint64_t rej[3][2], 
 }
 
 /* device bytes a stack call holds besides the frames: the output image (2 B per sample),
- * flag list and redo list (4 + 4 B), flag map (1 B), SUM's u32 sums (4 B), the literal
- * kernel's scratch, the readers' staging and the small tables */
+ * flag list and redo list (4 + 4 B), flag map (1 B), SUM's sums (4 B, 8 B past SG_SUM_U32_MAXN
+ * frames), the literal kernel's scratch, the readers' staging and the small tables */
 static size_t fixed_device_bytes(int N, int W, int H, int C) {
 	const size_t npix = (size_t)C * H * W;
-	return npix * 15 + lit_scratch_bytes(N) + ((size_t)4 << 20) +
+	return npix * (N > SG_SUM_U32_MAXN ? 19 : 15) + lit_scratch_bytes(N) + ((size_t)4 << 20) +
 		(size_t)SG_PULL_READERS * 2 * SG_PULL_CHUNK_BYTES;
 }
 
@@ -1183,7 +1188,7 @@ static int pull_device(sg_ctx *ctx, int g, PullCall &pc, int B, int E, int nread
 
 /* SUM over several devices: the 65535/max scaling of stack_summing (:328-342) with the maximum
  * over the whole image, applied to device g's rows [B, E) of raw sums */
-static int sum_finalize_rows(sg_ctx *ctx, int g, int W, int H, int C, int B, int E, unsigned int gmax) {
+static int sum_finalize_rows(sg_ctx *ctx, int g, int W, int H, int C, int B, int E, uint64_t gmax, bool wide) {
 	SgDevice &dv = ctx->dev[(size_t)g];
 	HIPCHK(hipSetDevice(dv.id));
 	SgStackParams p;
@@ -1197,8 +1202,8 @@ static int sum_finalize_rows(sg_ctx *ctx, int g, int W, int H, int C, int B, int
 	p.row_end = E;
 	p.maxim = flag_words(dv.ctr.p) + SG_FL_SUM_MAX;
 	HIPCHK(hipMemcpyAsync(p.maxim, &gmax, sizeof gmax, hipMemcpyHostToDevice, dv.stream));
-	hipLaunchKernelGGL(k_sum_finalize, dim3((unsigned)((W + 255) / 256), (unsigned)(E - B), (unsigned)C), dim3(256), 0,
-			dv.stream, p);
+	hipLaunchKernelGGL(wide ? k_sum_finalize_wide : k_sum_finalize, dim3((unsigned)((W + 255) / 256), (unsigned)(E - B),
+			(unsigned)C), dim3(256), 0, dv.stream, p);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(dv.stream));
 	return SG_OK;
@@ -1325,7 +1330,8 @@ extern "C" int sg_stack_u16(sg_ctx *ctx, const sg_stack_desc *d, sg_read_region_
 	for (int g = 0; g < G; g++)
 		gmax = std::max(gmax, mx[(size_t)g]);
 	for (int g = 0; g < G && late_copy; g++) {
-		if (int r = sum_finalize_rows(ctx, g, W, H, C, rb[(size_t)g], rb[(size_t)g + 1], (unsigned int)gmax))
+		if (int r = sum_finalize_rows(ctx, g, W, H, C, rb[(size_t)g], rb[(size_t)g + 1], gmax,
+				sg_sum_wide(d->method, N)))
 			return r;
 		if (int r = copy_out(g))
 			return r;

@@ -93,8 +93,8 @@ struct SgStackParams {
 	unsigned int *wx_count;
 	int wx_kmax;				/* export a column with 1 .. wx_kmax zero / 65535 samples (more: the rows a
 						 * registration shift empties, whose tiles are slow throughout: finished there) */
-	uint32_t *sum_buf;			/* SUM: raw sums [C][H][W] */
-	unsigned int *maxim;			/* SUM: global max of sums */
+	uint32_t *sum_buf;			/* SUM: raw sums [C][H][W] (unsigned long long in the wide kernels, sg_reduce_one) */
+	unsigned int *maxim;			/* SUM: global max of sums (8-byte aligned; unsigned long long in the wide kernels) */
 };
 
 /* pixel classes of this call (entries written by earlier calls read as SG_CLS_OK) */

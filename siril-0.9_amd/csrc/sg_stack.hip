@@ -941,8 +941,18 @@ template __global__ void k_stack_sorted<16, true>(SgStackParams, const unsigned 
 /* ----------------------------------------------------------------------------------
  * streaming reductions: SUM / MAX / MIN / MEAN(NO_REJEC)
  * ---------------------------------------------------------------------------------- */
-__global__ void __launch_bounds__(256)
-k_stack_reduce(SgStackParams p) {
+__device__ __forceinline__ uint32_t sg_shfl_down_acc(uint32_t v, int o) {
+	return (uint32_t)__shfl_down((int)v, o, 64);
+}
+__device__ __forceinline__ unsigned long long sg_shfl_down_acc(unsigned long long v, int o) {
+	return __shfl_down(v, o, 64);
+}
+
+/* ACC: the accumulator and SUM's raw sums and maximum.  uint32_t holds N 65535 up to N = 65537
+ * (2^32 - 1 exactly); a longer SUM or MEAN takes unsigned long long, as the reference's unsigned
+ * long sums (:196-355) and double mean (:1790-1794) have no cap (sg_plan_reduce_route: wide) */
+template <typename ACC>
+__device__ __forceinline__ void sg_reduce_one(const SgStackParams &p) {
 	const int x = blockIdx.x * 256 + threadIdx.x;
 	const int R = p.row_begin + blockIdx.y;
 	const int c = blockIdx.z;
@@ -953,7 +963,7 @@ k_stack_reduce(SgStackParams p) {
 	/* frames in batches of 16: every load of a batch is issued before any is used (an
 	 * out-of-frame sample loads a valid dummy address and is masked), so each wave keeps 16
 	 * row reads in flight */
-	uint32_t acc = (p.method == 4) ? 65535u : 0u;
+	ACC acc = (p.method == 4) ? 65535u : 0u;
 	/* the dummy address: a resident row of frame 0 (the base may be biased to a band) */
 	const int64_t dummy = (int64_t)p.res_begin * p.W;
 	for (int f0 = 0; f0 < N; f0 += 16) {
@@ -989,12 +999,12 @@ k_stack_reduce(SgStackParams p) {
 			}
 		}
 	}
-	unsigned int blockmax = 0;
+	ACC blockmax = 0;
 	if (live) {
 		if (p.method == 1) {
 			p.out[pix] = sg_round_to_WORD((double)acc / (double)N);
 		} else if (p.method == 0) {
-			p.sum_buf[pix] = acc;
+			((ACC *)p.sum_buf)[pix] = acc;
 			blockmax = acc;
 		} else {
 			p.out[pix] = (uint16_t)acc;
@@ -1002,12 +1012,23 @@ k_stack_reduce(SgStackParams p) {
 	}
 	if (p.method == 0) {
 		for (int o = 32; o > 0; o >>= 1) {
-			unsigned int t = (unsigned int)__shfl_down((int)blockmax, o, 64);
+			const ACC t = sg_shfl_down_acc(blockmax, o);
 			blockmax = t > blockmax ? t : blockmax;
 		}
 		if ((threadIdx.x & 63) == 0 && blockmax)
-			atomicMax(p.maxim, blockmax);
+			atomicMax((ACC *)p.maxim, blockmax);
 	}
+}
+
+__global__ void __launch_bounds__(256)
+k_stack_reduce(SgStackParams p) {
+	sg_reduce_one<uint32_t>(p);
+}
+
+/* N > 65537 frames of SUM / MEAN without rejection: 64-bit sums and maximum */
+__global__ void __launch_bounds__(256)
+k_stack_reduce_wide(SgStackParams p) {
+	sg_reduce_one<unsigned long long>(p);
 }
 
 /* The same reductions with a pixel PAIR per lane: one 4-byte buffer load per frame at the
@@ -1297,19 +1318,30 @@ SG_R3(3)
 SG_R3(4)
 #undef SG_R3
 
-/* SUM finalisation: out = round_to_WORD(sum) or round_to_WORD(sum * 65535/maxim) (:328-342) */
-__global__ void __launch_bounds__(256)
-k_sum_finalize(SgStackParams p) {
+/* SUM finalisation: out = round_to_WORD(sum) or round_to_WORD(sum * 65535/maxim) (:328-342);
+ * S: the width of the raw sums and of the maximum (sg_reduce_one) */
+template <typename S>
+__device__ __forceinline__ void sg_sum_finalize(const SgStackParams &p) {
 	const int x = blockIdx.x * 256 + threadIdx.x;
 	const int R = p.row_begin + blockIdx.y;
 	const int c = blockIdx.z;
 	if (x >= p.W)
 		return;
 	const int64_t pix = ((int64_t)c * p.H + R) * p.W + x;
-	const unsigned int maxim = *p.maxim;
+	const S maxim = *(const S *)p.maxim;
 	const double ratio = (maxim > 65535u) ? 65535.0 / (double)maxim : 1.0;
-	const uint32_t s = p.sum_buf[pix];
+	const S s = ((const S *)p.sum_buf)[pix];
 	p.out[pix] = (ratio == 1.0) ? sg_round_to_WORD((double)s) : sg_round_to_WORD((double)s * ratio);
+}
+
+__global__ void __launch_bounds__(256)
+k_sum_finalize(SgStackParams p) {
+	sg_sum_finalize<uint32_t>(p);
+}
+
+__global__ void __launch_bounds__(256)
+k_sum_finalize_wide(SgStackParams p) {
+	sg_sum_finalize<unsigned long long>(p);
 }
 
 /* ----------------------------------------------------------------------------------
@@ -3056,7 +3088,7 @@ k_stage_copy(uint4 *__restrict__ dst, const uint4 *__restrict__ src, unsigned in
 }
 
 /* host slot: rejection sums [3][2] u64 at 0, the flag block (flag / walk-fault / redo / compact
- * counts, loop fault, the SUM maximum at word 16) at byte 64; the device shards and flag words
+ * counts, loop fault, the SUM maximum at words 16 and 17) at byte 64; the device shards and flag words
  * 0..15 are zeroed for the slot's next call (the SUM maximum stays: a streamed SUM keeps it) */
 __global__ void __launch_bounds__(256)
 k_ctr_finalize(unsigned long long *__restrict__ ctr, unsigned long long *__restrict__ host) {

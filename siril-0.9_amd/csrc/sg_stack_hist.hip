@@ -773,7 +773,13 @@ __device__ __forceinline__ int sgh_value_at1(const SghPix &P, int g) {
  * steps on s ~ sqrt(x), h ~ 0.5 / sqrt(x): an initial relative error e becomes ~2 e^4, so a
  * few ulp in all), 8 dependent fp64 operations instead of the ~26 of an IEEE division and
  * square root.  The decisions keep a rounding band of 1e-13 relative (SGH_BAND), ~500 times
- * the error.  num < 2^53: num <= n^2 65535^2 / 4. */
+ * the error.  num = n SS - S^2 <= n^2 65535^2 / 4 is an exact integer, below 2^62 for the 65535
+ * frames the kernel takes, and its terms fit a long long: with the median in the band at most half
+ * the samples lie on either side of it, lo^2 + (65535 - lo)^2 <= 65535^2, so S^2 <= n SS <=
+ * n^2 65535^2 / 2 < 2^63.  num stays below 2^53, so that (double)num is exact, only up to
+ * n = 2896 for a column of counted zeros and 65535s; beyond, the conversion rounds by at most
+ * 2^-53 relative (2^-54 of sigma), far inside the band: the rounding band, not the redo list,
+ * keeps those decisions exact (tests/test_gpu_frame_counts.py: 3277, 4099 and 65535 frames). */
 __device__ __forceinline__ double sgh_sigma_fast(long long num, int n) {
 	const double nd = (double)(num > 0 ? num : 1);
 	const double x = nd * ((double)n * (double)(n - 1));

@@ -111,6 +111,14 @@ static size_t lit_scratch_bytes(int N) {
 	return (size_t)lit_thread_count(N) * (((size_t)N * 5 + 15) & ~(size_t)15);
 }
 
+/* SUM and MEAN without rejection add up to N samples of 65535 per pixel: N 65535 fits the reduce
+ * kernels' uint32_t sums up to N = 65537 (2^32 - 1 exactly).  The reference sums in unsigned long
+ * and double with no cap (stacking.c:196-355, :1790-1794), so a longer stack takes 64-bit sums */
+#define SG_SUM_U32_MAXN 65537
+static bool sg_sum_wide(int method, int N) {
+	return (method == SG_STACK_SUM || method == SG_STACK_MEAN) && N > SG_SUM_U32_MAXN;
+}
+
 /* the main kernel of a call */
 enum SgMainPath {
 	SG_MAIN_REDUCE = 0,	/* k_stack_reduce: SUM / MEAN / MAX / MIN, one pixel per lane */
@@ -119,7 +127,8 @@ enum SgMainPath {
 	SG_MAIN_SORTED,		/* k_stack_sorted<nreg, false> over every tile */
 	SG_MAIN_HIST,		/* k_stack_hist<rj, norm, ni> */
 	SG_MAIN_LINFIT,		/* k_stack_linfit<km, nw, pair> */
-	SG_MAIN_LITERAL_ALL	/* k_list_all: every pixel to the literal kernel */
+	SG_MAIN_LITERAL_ALL,	/* k_list_all: every pixel to the literal kernel */
+	SG_MAIN_REDUCE_WIDE	/* k_stack_reduce_wide: SUM / MEAN of more than SG_SUM_U32_MAXN frames, 64-bit sums */
 };
 /* where the redo list of the histogram / linfit kernels goes */
 enum SgRedoRoute {
@@ -157,7 +166,8 @@ struct SgStackPlan {
 	/* the route */
 	bool hist_addr_ok;		/* the shifted row offsets of a plane fit the 32-bit forms */
 	bool rejection_family;		/* MEDIAN or MEAN with rejection: flag map, chain tables, literal phases */
-	bool sum;			/* SUM: the u32 sums and the maximum */
+	bool sum;			/* SUM: the raw sums and the maximum */
+	bool wide;			/* SUM / MEAN without rejection past SG_SUM_U32_MAXN frames: 64-bit sums and maximum */
 	int main;			/* SgMainPath */
 	int nreg, rj, norm, ni, km, nw, seg, m;
 	bool pair;
@@ -548,12 +558,17 @@ static void sg_plan_reduce_route(const SgKnobs &k, SgStackPlan &pl) {
 	/* MEAN: the normalising instance's fp64 path costs registers: its own kernel */
 	pl.m = pl.method == SG_STACK_SUM ? 0 : pl.method == SG_STACK_MEAN ? (pl.normalize ? 2 : 1) :
 		pl.method == SG_STACK_MAX ? 3 : 4;
-	pl.main = r3 ? SG_MAIN_REDUCE3 : pairs ? SG_MAIN_REDUCE2 : SG_MAIN_REDUCE;
+	/* more frames than uint32_t sums hold: the one-pixel-per-lane kernel with 64-bit sums (any
+	 * plane size; MAX and MIN never overflow and keep their route) */
+	pl.wide = sg_sum_wide(pl.method, pl.N);
+	pl.main = pl.wide ? SG_MAIN_REDUCE_WIDE : r3 ? SG_MAIN_REDUCE3 : pairs ? SG_MAIN_REDUCE2 : SG_MAIN_REDUCE;
 	pl.fin_grid_x = (unsigned)((W + 255) / 256);
 	pl.main_threads = 256;
 	pl.main_grid[1] = (unsigned)nrows;
 	pl.main_grid[2] = (unsigned)C;
-	if (r3) {
+	if (pl.wide) {
+		pl.main_grid[0] = pl.fin_grid_x;
+	} else if (r3) {
 		pl.main_grid[0] = (unsigned)(((W + 512 * pl.seg - 1) / (512 * pl.seg)) * (size_t)nrows * C);
 		pl.main_grid[1] = pl.main_grid[2] = 1;
 	} else {

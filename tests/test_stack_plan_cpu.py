@@ -494,6 +494,41 @@ static void test_route_reduce(void) {
 	sh.shifts();
 	sh.sx[1] = 16384;
 	CHECK(sh.plan() == SG_OK && sh.pl.main == SG_MAIN_REDUCE2 && sh.pl.use_shift == 1);
+	/* N 65535 against the kernels' uint32_t sums: 65537 frames fit exactly and keep the route and the
+	 * grid of any shorter stack, 65538 take the 64-bit kernel (SUM and MEAN, normalised or not; MAX
+	 * and MIN add nothing up and stay) */
+	CHECK(65537ull * 65535ull == 0xFFFFFFFFull && SG_SUM_U32_MAXN == 65537);
+	for (int method : {SG_STACK_SUM, SG_STACK_MEAN, SG_STACK_MAX, SG_STACK_MIN})
+		for (int mode : {SG_NO_NORM, SG_ADDITIVE_SCALING}) {
+			const bool adds = method == SG_STACK_SUM || method == SG_STACK_MEAN;
+			const int mm = method == SG_STACK_SUM ? 0 : method == SG_STACK_MAX ? 3 : method == SG_STACK_MIN ? 4 :
+				mode == SG_NO_NORM ? 1 : 2;
+			Case ref(method, SG_NO_REJEC, 8, 1000, 10, 3), fit(method, SG_NO_REJEC, 65537, 1000, 10, 3),
+			     over(method, SG_NO_REJEC, 65538, 1000, 10, 3);
+			for (Case *c : {&ref, &fit, &over}) {
+				if (mode != SG_NO_NORM)
+					c->norm(mode);
+				CHECK(c->plan(2, 9) == SG_OK && c->pl.m == mm && c->pl.launches == 1 && c->pl.fin_grid_x == 4);
+				CHECK(c->pl.main_threads == 256 && c->pl.sum == (method == SG_STACK_SUM));
+			}
+			CHECK(!ref.pl.wide && !fit.pl.wide && over.pl.wide == adds);
+			CHECK(fit.pl.main == SG_MAIN_REDUCE3 && fit.pl.main == ref.pl.main && fit.pl.seg == ref.pl.seg);
+			CHECK(fit.pl.main_grid[0] == 42 && fit.pl.main_grid[1] == 1 && fit.pl.main_grid[2] == 1);
+			CHECK(fit.pl.main_kernel_blocks == 42 && ref.pl.main_kernel_blocks == 42);
+			if (adds) {
+				CHECK(over.pl.main == SG_MAIN_REDUCE_WIDE && over.pl.main_kernel_blocks == 84);
+				CHECK(over.pl.main_grid[0] == 4 && over.pl.main_grid[1] == 7 && over.pl.main_grid[2] == 3);
+			} else {
+				CHECK(over.pl.main == SG_MAIN_REDUCE3 && over.pl.main_grid[0] == 42 && over.pl.main_kernel_blocks == 42);
+			}
+			/* the knobs that pick the narrow kernels do not bring the uint32_t sums back */
+			over.k.reduce1 = 1;
+			CHECK(over.plan(2, 9) == SG_OK && over.pl.main == (adds ? SG_MAIN_REDUCE_WIDE : SG_MAIN_REDUCE));
+			fit.k.reduce1 = 1;
+			CHECK(fit.plan(2, 9) == SG_OK && fit.pl.main == SG_MAIN_REDUCE && !fit.pl.wide);
+		}
+	Case rj(SG_STACK_MEAN, SG_SIGMA, 65538, 64, 4);	/* a rejection stack has no sums to widen */
+	CHECK(rj.plan() == SG_OK && !rj.pl.wide && rj.pl.main == SG_MAIN_LITERAL_ALL);
 }
 
 static void test_errors(void) {
