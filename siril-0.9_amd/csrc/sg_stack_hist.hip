@@ -357,6 +357,28 @@ __device__ __forceinline__ int sgh_floor_clamp(double x) {
 	y = y < -1.0 ? -1.0 : y;
 	return (int)floor(y);
 }
+/* The SIGMA pass's forms of the two, fused with the integer clamp against the kept interval that
+ * always follows: max(sgh_ceil_clamp(x), A) for 0 <= A <= 65536 and min(sgh_floor_clamp(x), B)
+ * for -1 <= B <= 65535, for finite x (sigma is 0 for num <= 0, so the thresholds are).  ceil and
+ * floor commute with a clamp at integer bounds and v_cvt_i32_f64 saturates, so rounding, the
+ * saturating conversion and an integer min and max give the same integer as the clamp in
+ * doubles (7-8 VALU) followed by the integer max / min (tests/test_sat_clamp.py restates both
+ * forms).  An out-of-range (int) cast is undefined in C++, hence the instruction itself; no
+ * wait state is due between a VALU result and a plain VALU reader, and the compiler pads the
+ * statement's end for its own next instruction. */
+__device__ __forceinline__ int sgh_sat_i32(double y) {
+	int r;
+	asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(y));
+	return r;
+}
+__device__ __forceinline__ int sgh_ceil_sat_max(double x, int A) {
+	const int i = sgh_sat_i32(ceil(x));
+	return max(min(i, 65536), A);
+}
+__device__ __forceinline__ int sgh_floor_sat_min(double x, int B) {
+	const int i = sgh_sat_i32(floor(x));
+	return min(max(i, -1), B);
+}
 
 /* centre estimate of the two pixels of a lane from 16 samples each (16-bit halves of
  * p[]): median of the samples that are neither 0 nor 65535 (the out-of-frame zero fill of
@@ -846,29 +868,29 @@ __device__ __forceinline__ int sgh_sigma3(const SghPix &P, int N, double sl, dou
 		const double tl = sl * sigma, th = sh * sigma;
 		const double blo = median - tl, bhi = median + th;
 		const double tol = exact0 ? 0.0 : SGH_BAND * (fabs(median) + fabs(tl) + fabs(th) + 1.0);
-		int a = sgh_ceil_clamp(blo - tol);
-		a = a < A ? A : a;
-		int bt = sgh_floor_clamp(bhi + tol);
-		bt = bt > B ? B : bt;
+		const int a = sgh_ceil_sat_max(blo - tol, A);
+		const int bt = sgh_floor_sat_min(bhi + tol, B);
 		SghQ q;
 		sgh_q_load(P, half ? bt : a - 1, q);
 		if (zbad(half ? bt : a - 1))
 			zb = 1u;
 		const int cm = sgh_q_count(P, q), co = (int)sgh_x((uint32_t)cm);
 		const int cnt_a = half ? co : cm, cnt_bt = half ? cm : co;
+		/* the rounding band: half 0 tests amb1 = min(floor(blo + tol), B) (samples in [a, amb1]), half 1
+		 * amb0 = max(ceil(bhi - tol), A) (samples in [amb0, bt]).  One instruction stream serves both: with
+		 * ceil(x) = -floor(-x) and -(bhi - tol) = tol - bhi (rounding is symmetric), half 1 works on the
+		 * negated axis, e = -amb0 = min(max(floor(tol - bhi), -65536), -A) and amb0 <= bt is -bt <= e; the
+		 * count query is at amb1 or at amb0 - 1 = ~e */
 		uint32_t amb = 0;
 		if (!exact0) {
-			if (!half) {
-				int amb1 = sgh_floor_clamp(blo + tol);
-				amb1 = amb1 > B ? B : amb1;
-				amb = (a <= amb1 && sgh_cnt_le(P, amb1) - cnt_a > 0) ? 1u : 0u;
-				if (a <= amb1 && zbad(amb1))
-					zb = 1u;
-			} else {
-				int amb0 = sgh_ceil_clamp(bhi - tol);
-				amb0 = amb0 < A ? A : amb0;
-				amb = (amb0 <= bt && cnt_bt - sgh_cnt_le(P, amb0 - 1) > 0) ? 1u : 0u;
-				if (amb0 <= bt && zbad(amb0 - 1))
+			const double w = tol + (half ? -bhi : blo);
+			const int e = min(max(sgh_sat_i32(floor(w)), half ? -65536 : -1), half ? -A : B);
+			const bool need = (half ? -bt : a) <= e;
+			const int qv = half ? ~e : e;
+			if (need) {
+				const int c = sgh_cnt_le(P, qv);
+				amb = (half ? cm - c : c - cm) > 0 ? 1u : 0u;
+				if (zbad(qv))
 					zb = 1u;
 			}
 		}
