@@ -4,10 +4,13 @@
  * optionally register it with the DFT method, stack it with one of the five stackers and save
  * the result, timing each stage end to end (file reads included).
  *
- *   siril_cli (--ser FILE [--debayer P] | --fits F1 F2 ...) [--threads N]
+ *   siril_cli (--ser FILE [--debayer P [--bayer-inter N]] | --fits F1 F2 ...) [--threads N]
  *             [--register LAYER X Y SIZE] [--stack sum|mean|median|max|min]
  *             [--rejection none|percentile|sigma|sigmedian|winsorized|linearfit] [--sig LO HI]
  *             [--norm none|add|mul|addscale|mulscale] [--included] [-o OUT.fit]
+ *
+ * --bayer-inter N is com.debayer.bayer_inter for a demosaiced CFA SER: 0 bilinear (the default
+ * here), 1 nearest neighbour, 2 VNG; 3 (AHD) and 4 (super-pixel) are refused.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,6 +19,7 @@
 #include "siril_compat.h"
 
 sequence *harness_open_ser(const char *path, int debayer);
+sequence *harness_open_ser_inter(const char *path, int debayer, int inter);
 sequence *harness_open_fits(const char *const *paths, int n);
 void harness_close(sequence *seq);
 void harness_set_registration_layer(int layer);
@@ -46,7 +50,7 @@ int main(int argc, char **argv) {
 	static const char *const norm[] = { "none", "add", "mul", "addscale", "mulscale" };
 	const char *ser = NULL, *out = NULL;
 	const char **fitsv = NULL;
-	int nfits = 0, debayer = -2, method = -1, rejection = 2, normalize = 0, included = 0;
+	int nfits = 0, debayer = -2, inter = 0, method = -1, rejection = 2, normalize = 0, included = 0;
 	int reg = 0, rl = 0, rx = 0, ry = 0, rs = 0;
 	double sig[2] = { 4.0, 3.0 };
 	for (int i = 1; i < argc; i++) {
@@ -54,6 +58,8 @@ int main(int argc, char **argv) {
 			ser = argv[++i];
 		else if (!strcmp(argv[i], "--debayer") && i + 1 < argc)
 			debayer = atoi(argv[++i]);
+		else if (!strcmp(argv[i], "--bayer-inter") && i + 1 < argc)
+			inter = atoi(argv[++i]);
 		else if (!strcmp(argv[i], "--fits")) {
 			fitsv = (const char **)&argv[i + 1];
 			while (i + 1 < argc && argv[i + 1][0] != '-') {
@@ -87,7 +93,7 @@ int main(int argc, char **argv) {
 		}
 	}
 	double t0 = now_ms();
-	sequence *seq = ser ? harness_open_ser(ser, debayer) : nfits ? harness_open_fits(fitsv, nfits) : NULL;
+	sequence *seq = ser ? harness_open_ser_inter(ser, debayer, inter) : nfits ? harness_open_fits(fitsv, nfits) : NULL;
 	if (!seq) {
 		fprintf(stderr, "could not open the sequence\n");
 		return 3;

@@ -286,6 +286,27 @@ sequence *harness_open_ser(const char *path, int debayer) {
 	return new_sequence(gs, path, SEQ_SER);
 }
 
+/* the same with com.debayer.bayer_inter = inter (interpolation_method, src/core/siril.h:249-255:
+ * 0 bilinear, 1 nearest neighbour, 2 VNG, 3 AHD, 4 super-pixel).  Super-pixel is refused as
+ * stack_function_handler refuses it for a SER demosaiced on the fly (src/stacking/stacking.c:
+ * 1321-1325); AHD is refused by the library.  NULL on refusal: no other method is substituted. */
+sequence *harness_open_ser_inter(const char *path, int debayer, int inter) {
+	if (debayer < -1)
+		return harness_open_ser(path, debayer);
+	if (inter == SG_BAYER_SUPER_PIXEL) {
+		fprintf(stderr, "Super-pixel is not handled for on the fly SER stacking\n");
+		return NULL;
+	}
+	sg_seq *gs = NULL;
+	if (sg_seq_open_ser(path, &gs))
+		return NULL;
+	if (sg_seq_set_debayer_method(gs, debayer, inter)) {
+		sg_seq_close(gs);
+		return NULL;
+	}
+	return new_sequence(gs, path, SEQ_SER);
+}
+
 sequence *harness_open_fits(const char *const *paths, int n) {
 	sg_seq *gs = NULL;
 	if (sg_seq_open_fits(paths, n, &gs))

@@ -78,6 +78,56 @@ enum { SG_BAYER_RGGB = 0, SG_BAYER_BGGR = 1, SG_BAYER_GBRG = 2, SG_BAYER_GRBG = 
 int sg_seq_set_debayer(sg_seq *seq, int pattern);
 
 /*
+ * The same with the interpolation of com.debayer.bayer_inter (interpolation_method,
+ * src/core/siril.h:249-255; the reference's default is BAYER_VNG, src/io/conversion.c:252).
+ * sg_seq_set_debayer(seq, p) stays and means SG_BAYER_BILINEAR.
+ *
+ * SG_BAYER_NEARESTNEIGHBOR (bayer_NearestNeighbor, demosaicing.c:177-244): pixel (y, x), y <= H-2
+ * and x <= W-2, takes its colours from the 2x2 cell whose top-left corner it is; the LAST row and
+ * column stay 0.
+ * SG_BAYER_VNG (bayer_VNG :284-420): bayer_Bilinear, then on rows 2..H-3, columns 2..W-3 the
+ * threshold-gradient average over the 5x5 bilinear neighbourhood; the two-pixel ring keeps the
+ * bilinear values (its one-pixel border 0).
+ *
+ * The reference's three read paths do not agree with each other under VNG, and each is
+ * reproduced as it is:
+ *   1. whole frame (sg_seq_read_frame, sg_seq_read_selection, sg_seq_load_device; ser_read_frame
+ *      -> debayer(), ser.c:708-737, demosaicing.c:729-768): the frame is demosaiced as one image,
+ *      and for an 8-bit SER every sample goes through round_to_BYTE, so VNG's overshoots above
+ *      255 are clamped to 255;
+ *   2. region (sg_seq_read_region; ser_read_opened_partial's CFA branch, ser.c:820-913): the rows
+ *      of the band, widened by get_debayer_area (demosaicing.c:787-842: 2 or 3 rows on each side,
+ *      less at the frame's edges), are demosaiced AS AN IMAGE OF THEIR OWN and the layer is
+ *      cropped, with no round_to_BYTE: 8-bit regions can hold values above 255.  VNG's outermost
+ *      rows read the area's own zero bilinear border, so the first or last row of a band can
+ *      differ from the same row of the whole frame, depending on the parity of the band's first
+ *      and last row; an area under 6 rows (a band of 1 or 2 rows at the frame's top or bottom)
+ *      gets rows of zeros at columns 2..W-3 from the reference's delay buffer.  A stack fed by
+ *      this reader (sg_stack_u16) therefore depends on how the rows were cut into bands, as the
+ *      reference's own does on its row blocks; the device load (1.) does not;
+ *   3. under nearest neighbour the widening keeps the area's zero row away from the band, and the
+ *      region rows equal the whole frame's.
+ * The reference's crop adds the area's x offset in elements instead of pixels (ser.c:907), so a
+ * partial-width area is garbage there: under these two methods sg_seq_read_region accepts
+ * full-width areas only (area->x == 0 && area->w == width) and returns -1 otherwise.  Bilinear
+ * region reads are as before.
+ *
+ * Returns 0, or
+ *   SG_ERR_GENERIC  SG_BAYER_AHD: it goes through a cube-root table built with pow() and float
+ *                   CIELab (demosaicing.c:422-660), so its bits rest on the libm in use and
+ *                   cannot be pinned;
+ *   SG_ERR_GENERIC  SG_BAYER_SUPER_PIXEL: it halves the frame size, and the reference refuses it
+ *                   for stacking a SER on the fly (src/stacking/stacking.c:1321-1325);
+ *   SG_ERR_GENERIC  any other interpolation value (the reference's debayer_buffer would fall to
+ *                   VNG; an unknown setting is refused here rather than guessed), a bad pattern,
+ *                   or a sequence that is not a CFA SER;
+ *   SG_ERR_SIZE     SG_BAYER_VNG on a frame under 6x6: the VNG pass has no pixel of its own there.
+ * A refused method is never replaced by another one; the sequence is left as it was.
+ */
+enum { SG_BAYER_BILINEAR = 0, SG_BAYER_NEARESTNEIGHBOR = 1, SG_BAYER_VNG = 2, SG_BAYER_AHD = 3, SG_BAYER_SUPER_PIXEL = 4 };
+int sg_seq_set_debayer_method(sg_seq *seq, int pattern, int interpolation);
+
+/*
  * Siril .seq files (readseqfile / writeseqfile, src/io/seqfile.c:43-357): the sequence
  * description with the cached per-image statistics (I lines: mean median sigma avgDev mad
  * sqrtbwmv location scale min max, written with %g) and the registration data (R lines).

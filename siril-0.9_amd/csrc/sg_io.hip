@@ -19,6 +19,13 @@
  *     de-interleaving and the SER top-down -> bottom-up flip in one pass (one thread per
  *     output sample, coalesced writes), writing frames at a caller-chosen stride so they
  *     land directly in the stacking layout.
+ * CFA SER opened with demosaicing (sg_seq_set_debayer / sg_seq_set_debayer_method): bilinear
+ *   (k_debayer_frames, debayer_rows_host), nearest neighbour (k_debayer_nn) and VNG
+ *   (k_debayer_vng); the latter two share their per-pixel rules between host and device through
+ *   sg_debayer.h, and their host reads go through debayer_area_host, which demosaics an area of
+ *   rows as an image of its own: the whole frame for sg_seq_read_frame / _selection, the widened
+ *   band for sg_seq_read_region.  Under VNG those two differ (sirilgpu_io.h); AHD and
+ *   super-pixel are refused.
  */
 #include "sg_common.hpp"
 #include "sg_ctx.hpp"
@@ -46,6 +53,7 @@ struct sg_seq {
 	int bgr;
 	int color_id, bitpix, bzero;
 	int debayer;		/* -1, or the SG_BAYER_* pattern of a demosaiced CFA SER */
+	int inter;		/* its interpolation: SG_BAYER_BILINEAR / _NEARESTNEIGHBOR / _VNG */
 	std::vector<int> fd;	/* SER: one; FITS: one per frame */
 	std::vector<int64_t> data_off;	/* byte offset of the pixel data (per file) */
 	std::vector<std::string> cards;	/* FITS: the value cards of each file's primary header (80 B each) */
@@ -53,6 +61,7 @@ struct sg_seq {
 };
 
 #include "../../include/sirilgpu_io.h"
+#include "sg_debayer.h"
 
 static int rd_exact(int fd, void *buf, size_t n, int64_t off) {
 	char *p = (char *)buf;
@@ -171,6 +180,7 @@ static int sg_seq_open_ser_impl(const char *path, sg_seq **out) {
 	}
 	s->kind = SG_SRC_SER;
 	s->debayer = -1;
+	s->inter = SG_BAYER_BILINEAR;
 	/* the 7 little-endian ints at byte 14 (ser.c:312) */
 	s->color_id = (int)le32(h + 18);
 	const int big = (int)le32(h + 22) == 1;	/* SER_BIG_ENDIAN = 1 (ser.h:41) */
@@ -259,6 +269,7 @@ static int sg_seq_open_fits_impl(const char *const *paths, int nframes, sg_seq *
 		return SG_ERR_SIZE;
 	s->kind = SG_SRC_FITS;
 	s->debayer = -1;
+	s->inter = SG_BAYER_BILINEAR;
 	for (int i = 0; i < nframes; i++) {
 		int fd = open(paths[i], O_RDONLY);
 		if (fd < 0) {
@@ -418,8 +429,102 @@ extern "C" int sg_seq_set_debayer(sg_seq *s, int pattern) {
 		pattern = from_id[s->color_id - 8];
 	}
 	s->debayer = pattern;
+	s->inter = SG_BAYER_BILINEAR;
 	s->layers = 3;	/* frame_bytes stays the raw CFA frame */
 	return SG_OK;
+}
+
+extern "C" int sg_seq_set_debayer_method(sg_seq *s, int pattern, int interpolation) {
+	/* AHD and super-pixel are refused, not replaced by another method (sirilgpu_io.h) */
+	if (interpolation != SG_BAYER_BILINEAR && interpolation != SG_BAYER_NEARESTNEIGHBOR && interpolation != SG_BAYER_VNG)
+		return SG_ERR_GENERIC;
+	if (!s || s->kind != SG_SRC_SER || s->color_id < 8 || s->color_id > 11 || pattern < -1 || pattern > 3)
+		return SG_ERR_GENERIC;
+	/* VNG works on rows 2..H-3, columns 2..W-3 behind a three-row delay buffer: under 6 rows the
+	 * buffer's write-back zeroes rows instead, and under 4 columns the row copies have a negative
+	 * length; the per-pixel form of the kernel holds from 6x6 */
+	if (interpolation == SG_BAYER_VNG && (s->width < 6 || s->height < 6))
+		return SG_ERR_SIZE;
+	const int rc = sg_seq_set_debayer(s, pattern);
+	if (rc == SG_OK)
+		s->inter = interpolation;
+	return rc;
+}
+
+/* get_debayer_area (src/algos/demosaicing.c:787-842) for a full-width band: rows [*ay, *ay + *ah)
+ * to demosaic for top-down rows y .. y + h - 1, and the band's first row in that area.  The
+ * area starts on an even row 2 or 3 above (or at row 0) and ends 2 or 3 rows below (or at the
+ * last row). */
+static void debayer_area_rows(int y, int h, int H, int *ay, int *ah, int *yoff) {
+	int top = (y & 1) ? 3 : 2;
+	if (y - top < 0)
+		top = y;
+	const int yend = y + h - 1;
+	int bottom = (yend & 1) ? 2 : 3;
+	if (yend + bottom >= H)
+		bottom = H - yend - 1;
+	*ay = y - top;
+	*yoff = top;
+	*ah = h + top + bottom;
+}
+
+/* debayer_buffer (src/algos/demosaicing.c:667-727) with BAYER_NEARESNEIGHBOR or BAYER_VNG on
+ * top-down rows [ay, ay + ah) of a CFA frame, full width, AS AN IMAGE OF ITS OWN: interleaved
+ * RGB, [ah][W][3].  Nearest neighbour leaves the area's last row and column 0.  VNG computes
+ * bilinear with the area's own zero border, then the VNG pass on rows 2..ah-3, columns 2..W-3 of
+ * the area (sg_debayer.h).  An area under 6 rows gets what the reference's delay buffer writes
+ * back (:407-416): its still-zero rows land on rows 0 and 1 (ah = 3, 4), or on row 1 with
+ * VNG on row 2 (ah = 5), at columns 2..W-3. */
+static int debayer_area_host(const sg_seq *s, int index, int ay, int ah, std::vector<uint16_t> &rgb) {
+	const int W = s->width, bps = s->bytes_per_sample, pat = s->debayer;
+	if (ah < 1 || (s->inter == SG_BAYER_VNG && (ah < 3 || W < 6)))
+		return -1;
+	std::vector<unsigned char> raw((size_t)ah * W * bps);
+	if (rd_exact(s->fd[0], raw.data(), raw.size(), s->data_off[0] + s->frame_bytes * (int64_t)index + (int64_t)ay * W * bps))
+		return -1;
+	int bad = 0;
+	std::vector<uint16_t> cfa((size_t)ah * W);
+	for (size_t i = 0; i < cfa.size(); i++)
+		cfa[i] = conv_host(&raw[i * bps], s->enc, &bad);
+	rgb.assign((size_t)ah * W * 3, 0);
+	const bool nn = s->inter == SG_BAYER_NEARESTNEIGHBOR;
+	/* the area starts on an even row, so the area's parities are the frame's */
+	for (int y = nn ? 0 : 1; y <= ah - 2; y++)
+		for (int x = nn ? 0 : 1; x <= W - 2; x++) {
+			auto at = [&](int dy, int dx) -> int { return cfa[(size_t)(y + dy) * W + x + dx]; };
+			int px[3] = {0, 0, 0};
+			const int col = sg_cfa_color(pat, y, x), rowc = sg_cfa_color(pat, y, x + 1);
+			if (nn)
+				sg_nn_px(col, rowc, at, px);
+			else
+				sg_bilinear_px(col, rowc, at, px);
+			for (int c = 0; c < 3; c++)
+				rgb[((size_t)y * W + x) * 3 + c] = (uint16_t)px[c];
+		}
+	if (nn)
+		return bad ? -1 : 0;
+	const std::vector<uint16_t> bil(rgb);
+	auto vng_row = [&](int y) {
+		for (int x = 2; x <= W - 3; x++) {
+			auto B = [&](int dy, int dx, int c) -> int { return bil[((size_t)(y + dy) * W + x + dx) * 3 + c]; };
+			int px[3];
+			sg_vng_px_any(pat, y, x, B, px);
+			for (int c = 0; c < 3; c++)
+				rgb[((size_t)y * W + x) * 3 + c] = (uint16_t)px[c];
+		}
+	};
+	auto zero_row = [&](int y) { std::fill(rgb.begin() + ((size_t)y * W + 2) * 3, rgb.begin() + ((size_t)y * W + W - 2) * 3, (uint16_t)0); };
+	if (ah >= 6) {
+		for (int y = 2; y <= ah - 3; y++)
+			vng_row(y);
+	} else if (ah == 5) {
+		zero_row(1);
+		vng_row(2);
+	} else {
+		zero_row(0);
+		zero_row(1);
+	}
+	return bad ? -1 : 0;
 }
 
 /* bayer_Bilinear (src/algos/demosaicing.c:89-176) on the host for top-down rows [ty0, ty1),
@@ -472,6 +577,22 @@ static int sg_seq_read_region_impl(void *user, int layer, int index, uint16_t *b
 	if (area->x < 0 || area->y < 0 || area->w <= 0 || area->h <= 0 || area->x + area->w > s->width ||
 			area->y + area->h > s->height)
 		return -1;
+	if (s->debayer >= 0 && s->inter != SG_BAYER_BILINEAR) {
+		/* ser_read_opened_partial's CFA branch (ser.c:820-913): the widened area demosaiced as
+		 * an image of its own, no round_to_BYTE, then the layer cropped.  Its crop adds the x
+		 * offset in elements, not pixels (:907), so only full-width areas are defined */
+		if (area->x != 0 || area->w != s->width)
+			return -1;
+		int ay, ah, yoff;
+		debayer_area_rows(area->y, area->h, s->height, &ay, &ah, &yoff);
+		std::vector<uint16_t> rgb;
+		if (debayer_area_host(s, index, ay, ah, rgb))
+			return -1;
+		for (int r = 0; r < area->h; r++)
+			for (int x = 0; x < area->w; x++)
+				buffer[(size_t)r * area->w + x] = rgb[((size_t)(yoff + r) * s->width + x) * 3 + layer];
+		return 0;
+	}
 	if (s->debayer >= 0)	/* CFA SER opened with demosaicing: top-down rows y .. y+h-1 */
 		return debayer_rows_host(s, index, layer, area->y, area->y + area->h, area->x, area->w, buffer);
 	const int bps = s->bytes_per_sample;
@@ -518,6 +639,20 @@ extern "C" int sg_seq_read_region(void *user, int layer, int index, uint16_t *bu
 static int sg_seq_read_frame_impl(const sg_seq *s, int index, uint16_t *out) {
 	if (!s || !out || index < 0 || index >= s->frames)
 		return SG_ERR_GENERIC;
+	if (s->debayer >= 0 && s->inter != SG_BAYER_BILINEAR) {
+		/* debayer() (demosaicing.c:729-768) on the whole frame: an 8-bit SER goes through
+		 * round_to_BYTE, which clamps VNG's overshoots to 255; then the flip */
+		const int W = s->width, H = s->height;
+		std::vector<uint16_t> rgb;
+		if (debayer_area_host(s, index, 0, H, rgb))
+			return SG_ERR_READ;
+		const uint16_t top = s->bytes_per_sample == 1 ? 255 : 65535;
+		for (int c = 0; c < 3; c++)
+			for (int r = 0; r < H; r++)
+				for (int x = 0; x < W; x++)
+					out[((size_t)c * H + r) * W + x] = std::min(rgb[((size_t)(H - 1 - r) * W + x) * 3 + c], top);
+		return SG_OK;
+	}
 	if (s->debayer >= 0) {	/* ser_read_frame: debayer() then fits_flip_top_to_bottom (ser.c:730,758) */
 		const int W = s->width, H = s->height;
 		std::vector<uint16_t> td((size_t)W * H);
@@ -594,6 +729,17 @@ static int sg_seq_read_selection_impl(const sg_seq *s, int layer, int index, con
 	const int m0 = H - a->y - a->h;
 	if (a->x < 0 || a->x + a->w > W || a->y < 0 || m0 < 0)
 		return SG_ERR_GENERIC;
+	if (s->debayer >= 0 && s->inter != SG_BAYER_BILINEAR) {
+		/* the whole frame as ser_read_frame gives it (8-bit clamp included), not the region
+		 * reader's area: under VNG the two differ */
+		std::vector<uint16_t> fr((size_t)3 * W * H);
+		const int rc = sg_seq_read_frame_impl(s, index, fr.data());
+		if (rc)
+			return rc;
+		for (int r = 0; r < a->h; r++)
+			memcpy(out + (size_t)r * a->w, fr.data() + ((size_t)layer * H + m0 + r) * W + a->x, (size_t)a->w * sizeof(uint16_t));
+		return SG_OK;
+	}
 	std::vector<uint16_t> td((size_t)a->w * a->h);
 	const sg_rect band = {a->x, a->y, a->w, a->h};	/* top-down rows y .. y + h - 1 */
 	const int rc = sg_seq_read_region_impl((void *)s, layer, index, td.data(), &band);
@@ -712,6 +858,130 @@ __global__ void __launch_bounds__(256) k_debayer_frames(SgDecode d, int pattern)
 		atomicOr(d.bad, 1u);
 }
 
+/* bayer_NearestNeighbor (src/algos/demosaicing.c:177-244) per output pixel, in the shape of
+ * k_debayer_frames: pixels y <= H-2, x <= W-2 take the colours of the 2x2 cell they head
+ * (sg_nn_px), the last row and column stay 0 */
+__global__ void __launch_bounds__(256) k_debayer_nn(SgDecode d, int pattern) {
+	const int64_t plane = (int64_t)d.W * d.H;
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	const int f = blockIdx.y;
+	if (i >= plane)
+		return;
+	const int ty = (int)(i / d.W), x = (int)(i - (int64_t)ty * d.W);	/* top-down */
+	const int bps = d.enc == SG_ENC_U8 ? 1 : 2;
+	const unsigned char *raw = d.raw + (int64_t)f * d.raw_frame_bytes;
+	bool bad = false;
+	auto at = [&](int dy, int dx) -> int { return sg_conv(raw + ((int64_t)(ty + dy) * d.W + x + dx) * bps, d.enc, bad); };
+	int rgb[3] = {0, 0, 0};
+	if (ty <= d.H - 2 && x <= d.W - 2)
+		sg_nn_px(sg_cfa_color(pattern, ty, x), sg_cfa_color(pattern, ty, x + 1), at, rgb);
+	const int64_t o = (int64_t)(d.H - 1 - ty) * d.W + x;
+	uint16_t *out = d.out + (int64_t)f * d.out_frame_stride;
+	for (int k = 0; k < 3; k++)
+		out[(int64_t)k * plane + o] = (uint16_t)rgb[k];
+	if (bad)
+		atomicOr(d.bad, 1u);
+}
+
+/* bayer_VNG (src/algos/demosaicing.c:284-420) of whole frames.  One workgroup of 256 threads
+ * makes one SG_VNG_TW x SG_VNG_TH tile of frame blockIdx.z:
+ *   1. the tile's CFA samples with a 3-pixel halo are decoded once into LDS (0 outside the frame);
+ *   2. the bilinear image of the tile with a 2-pixel halo goes to LDS as three planes, 0 outside
+ *      rows 1..H-2, columns 1..W-2: VNG at row 2 reads the frame's real zero border;
+ *   3. VNG (sg_vng_px) reads its 5x5 bilinear neighbourhood from LDS.
+ * In steps 2 and 3 a thread owns whole 2x2 CFA quads and does their four sites one after the
+ * other, so all lanes of a wave are on the same site of the pattern at the same time and each
+ * site's terms are straight-line code with constant LDS offsets (the tile origin is even).
+ * The u16 planes put the quads of one row of a wave on consecutive LDS banks.
+ * Pixels outside rows 2..H-3, columns 2..W-3 keep the bilinear value; `top` = 255 for an 8-bit
+ * SER (debayer()'s round_to_BYTE, :755-765), else 65535.  Output: planes R, G, B, bottom-up. */
+#define SG_VNG_TW 64
+#define SG_VNG_TH 16
+#define SG_VNG_RAW_W (SG_VNG_TW + 6)
+#define SG_VNG_RAW_H (SG_VNG_TH + 6)
+#define SG_VNG_BIL_W (SG_VNG_TW + 4)
+#define SG_VNG_BIL_H (SG_VNG_TH + 4)
+
+struct SgVngLds {
+	const uint16_t *p;	/* the centre pixel in plane 0 */
+	__device__ __forceinline__ int operator()(int dy, int dx, int c) const {
+		return p[c * (SG_VNG_BIL_W * SG_VNG_BIL_H) + dy * SG_VNG_BIL_W + dx];
+	}
+};
+
+template <int PAT, int PY, int PX>
+__device__ __forceinline__ void vng_bilinear_site(const uint16_t *s_raw, uint16_t *s_bil, int ly, int lx, int y, int x, int H,
+		int W) {
+	int rgb[3] = {0, 0, 0};
+	if (y >= 1 && y <= H - 2 && x >= 1 && x <= W - 2) {
+		const uint16_t *r = s_raw + (ly + 1) * SG_VNG_RAW_W + lx + 1;
+		auto at = [&](int dy, int dx) -> int { return r[dy * SG_VNG_RAW_W + dx]; };
+		sg_bilinear_px(sg_cfa_color(PAT, PY, PX), sg_cfa_color(PAT, PY, PX + 1), at, rgb);
+	}
+	for (int c = 0; c < 3; c++)
+		s_bil[c * (SG_VNG_BIL_W * SG_VNG_BIL_H) + ly * SG_VNG_BIL_W + lx] = (uint16_t)rgb[c];
+}
+
+template <int PAT, int PY, int PX>
+__device__ __forceinline__ void vng_site(const uint16_t *s_bil, uint16_t *out, int64_t plane, int ly, int lx, int y, int x,
+		int H, int W, int top) {
+	if (y >= H || x >= W)
+		return;
+	const SgVngLds B = {s_bil + (ly + 2) * SG_VNG_BIL_W + lx + 2};
+	int rgb[3];
+	if (y >= 2 && y <= H - 3 && x >= 2 && x <= W - 3)
+		sg_vng_px<PAT, PY, PX>(B, rgb);
+	else
+		for (int c = 0; c < 3; c++)
+			rgb[c] = B(0, 0, c);
+	const int64_t o = (int64_t)(H - 1 - y) * W + x;
+	for (int c = 0; c < 3; c++)
+		out[(int64_t)c * plane + o] = (uint16_t)(rgb[c] > top ? top : rgb[c]);
+}
+
+template <int PAT>
+__global__ void __launch_bounds__(256) k_debayer_vng(SgDecode d, int top) {
+	__shared__ uint16_t s_raw[SG_VNG_RAW_W * SG_VNG_RAW_H];
+	__shared__ uint16_t s_bil[3 * SG_VNG_BIL_W * SG_VNG_BIL_H];
+	const int tid = threadIdx.x, H = d.H, W = d.W;
+	const int x0 = blockIdx.x * SG_VNG_TW, y0 = blockIdx.y * SG_VNG_TH;	/* top-down, both even */
+	const int bps = d.enc == SG_ENC_U8 ? 1 : 2;
+	const unsigned char *raw = d.raw + (int64_t)blockIdx.z * d.raw_frame_bytes;
+	bool bad = false;
+	for (int i = tid; i < SG_VNG_RAW_W * SG_VNG_RAW_H; i += 256) {
+		const int ry = i / SG_VNG_RAW_W, rx = i - ry * SG_VNG_RAW_W;
+		const int y = y0 - 3 + ry, x = x0 - 3 + rx;
+		uint16_t v = 0;
+		if (y >= 0 && y < H && x >= 0 && x < W)
+			v = sg_conv(raw + ((int64_t)y * W + x) * bps, d.enc, bad);
+		s_raw[i] = v;
+	}
+	__syncthreads();
+	/* bilinear quads of the (TH + 4) x (TW + 4) region whose corner is (y0 - 2, x0 - 2) */
+	for (int q = tid; q < (SG_VNG_BIL_W / 2) * (SG_VNG_BIL_H / 2); q += 256) {
+		const int qy = q / (SG_VNG_BIL_W / 2), qx = q - qy * (SG_VNG_BIL_W / 2);
+		const int ly = 2 * qy, lx = 2 * qx, y = y0 - 2 + ly, x = x0 - 2 + lx;
+		vng_bilinear_site<PAT, 0, 0>(s_raw, s_bil, ly, lx, y, x, H, W);
+		vng_bilinear_site<PAT, 0, 1>(s_raw, s_bil, ly, lx + 1, y, x + 1, H, W);
+		vng_bilinear_site<PAT, 1, 0>(s_raw, s_bil, ly + 1, lx, y + 1, x, H, W);
+		vng_bilinear_site<PAT, 1, 1>(s_raw, s_bil, ly + 1, lx + 1, y + 1, x + 1, H, W);
+	}
+	__syncthreads();
+	{
+		const int ly = 2 * (tid / (SG_VNG_TW / 2)), lx = 2 * (tid % (SG_VNG_TW / 2)), y = y0 + ly, x = x0 + lx;
+		uint16_t *out = d.out + (int64_t)blockIdx.z * d.out_frame_stride;
+		const int64_t plane = (int64_t)W * H;
+		vng_site<PAT, 0, 0>(s_bil, out, plane, ly, lx, y, x, H, W, top);
+		vng_site<PAT, 0, 1>(s_bil, out, plane, ly, lx + 1, y, x + 1, H, W, top);
+		vng_site<PAT, 1, 0>(s_bil, out, plane, ly + 1, lx, y + 1, x, H, W, top);
+		vng_site<PAT, 1, 1>(s_bil, out, plane, ly + 1, lx + 1, y + 1, x + 1, H, W, top);
+	}
+	if (bad)
+		atomicOr(d.bad, 1u);
+}
+static_assert((SG_VNG_TW / 2) * (SG_VNG_TH / 2) == 256 && SG_VNG_TW % 2 == 0 && SG_VNG_TH % 2 == 0,
+		"one 2x2 quad per thread of k_debayer_vng");
+
 /* host-pull path (sg_stack_u16): a top-down chunk of `rows` rows as the region callback
  * returned it (seq_opened_read_region, src/io/sequence.c:690-700) -> memory rows (bottom-up,
  * the stacking layout) of a frame plane: src row t lands at dst row rows - 1 - t.  The flip
@@ -788,7 +1058,30 @@ extern "C" int sg_seq_load_device(sg_ctx *ctx, int dev_index, const sg_seq *s, i
 		d.ser = s->kind == SG_SRC_SER;
 		d.nframes = n;
 		d.bad = (unsigned int *)dv.io_bad.p;
-		if (s->debayer >= 0)
+		if (s->debayer >= 0 && s->inter == SG_BAYER_VNG) {
+			const dim3 grid((unsigned)((s->width + SG_VNG_TW - 1) / SG_VNG_TW), (unsigned)((s->height + SG_VNG_TH - 1) / SG_VNG_TH),
+					(unsigned)n);
+			const int top = s->bytes_per_sample == 1 ? 255 : 65535;
+			if (grid.y > 65535u)
+				return set_err(ctx, SG_ERR_SIZE, "frame too tall for the VNG kernel%s (%ld rows)", "", (long)s->height);
+			switch (s->debayer) {
+			case SG_BAYER_RGGB:
+				hipLaunchKernelGGL(k_debayer_vng<SG_BAYER_RGGB>, grid, dim3(256), 0, st, d, top);
+				break;
+			case SG_BAYER_BGGR:
+				hipLaunchKernelGGL(k_debayer_vng<SG_BAYER_BGGR>, grid, dim3(256), 0, st, d, top);
+				break;
+			case SG_BAYER_GBRG:
+				hipLaunchKernelGGL(k_debayer_vng<SG_BAYER_GBRG>, grid, dim3(256), 0, st, d, top);
+				break;
+			default:
+				hipLaunchKernelGGL(k_debayer_vng<SG_BAYER_GRBG>, grid, dim3(256), 0, st, d, top);
+				break;
+			}
+		} else if (s->debayer >= 0 && s->inter == SG_BAYER_NEARESTNEIGHBOR)
+			hipLaunchKernelGGL(k_debayer_nn, dim3((unsigned)(((int64_t)s->width * s->height + 255) / 256), (unsigned)n),
+					dim3(256), 0, st, d, s->debayer);
+		else if (s->debayer >= 0)
 			hipLaunchKernelGGL(k_debayer_frames, dim3((unsigned)(((int64_t)s->width * s->height + 255) / 256), (unsigned)n),
 					dim3(256), 0, st, d, s->debayer);
 		else

@@ -87,7 +87,7 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_get_last_stats", "sg_register_dft_u16", "sg_register_dft_u16_device",
            "sg_register_dft_u16_device_raw", "sg_register_dft_u16_device_pitched", "sg_synth_fill_device",
            "sg_seq_open_ser", "sg_seq_open_fits", "sg_seq_close", "sg_seq_get_info", "sg_seq_read_region",
-           "sg_seq_read_frame", "sg_seq_load_device", "sg_seq_set_debayer", "sg_warp_u16", "sg_warp_u16_device",
+           "sg_seq_read_frame", "sg_seq_load_device", "sg_seq_set_debayer", "sg_seq_set_debayer_method", "sg_warp_u16", "sg_warp_u16_device",
            "sg_frame_stats_ikss_device", "sg_compute_normalization", "sg_seqfile_read", "sg_seqfile_create",
            "sg_seqfile_free", "sg_seqfile_get_info", "sg_seqfile_get_images", "sg_seqfile_set_image",
            "sg_seqfile_get_registration", "sg_seqfile_set_registration", "sg_seqfile_write"]
@@ -187,6 +187,8 @@ def load():
     lib.sg_seqfile_write.argtypes = [P, ctypes.c_char_p]
     lib.sg_seq_set_debayer.argtypes = [P, ctypes.c_int]
     lib.sg_seq_set_debayer.restype = ctypes.c_int
+    lib.sg_seq_set_debayer_method.argtypes = [P, ctypes.c_int, ctypes.c_int]
+    lib.sg_seq_set_debayer_method.restype = ctypes.c_int
     lib.sg_warp_u16.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.c_int, ctypes.c_int,
                                 ctypes.POINTER(ctypes.c_double), ctypes.c_int]
     lib.sg_warp_u16.restype = ctypes.c_int
@@ -292,6 +294,8 @@ class SeqFile:
 
 # sensor_pattern (src/core/siril.h:266-271)
 BAYER_RGGB, BAYER_BGGR, BAYER_GBRG, BAYER_GRBG = 0, 1, 2, 3
+# interpolation_method (src/core/siril.h:249-255)
+BAYER_INTER_BILINEAR, BAYER_INTER_NEARESTNEIGHBOR, BAYER_INTER_VNG, BAYER_INTER_AHD, BAYER_INTER_SUPER_PIXEL = range(5)
 
 
 class Seq:
@@ -337,11 +341,13 @@ class Seq:
     def __exit__(self, *a):
         self.close()
 
-    def set_debayer(self, pattern=-1):
-        """demosaic a CFA SER on device loads (bilinear); pattern BAYER_* or -1 = from the header"""
-        rc = self.lib.sg_seq_set_debayer(self.h, pattern)
+    def set_debayer(self, pattern=-1, interpolation=BAYER_INTER_BILINEAR):
+        """demosaic a CFA SER on host reads and device loads; pattern BAYER_* or -1 = from the
+        header; interpolation BAYER_INTER_BILINEAR, _NEARESTNEIGHBOR or _VNG (AHD and super-pixel
+        are refused, see include/sirilgpu_io.h)"""
+        rc = self.lib.sg_seq_set_debayer_method(self.h, pattern, interpolation)
         if rc != SG_OK:
-            raise RuntimeError(f"sg_seq_set_debayer failed ({rc})")
+            raise RuntimeError(f"sg_seq_set_debayer_method failed ({rc})")
         info = SeqInfo()
         self.lib.sg_seq_get_info(self.h, ctypes.byref(info))
         self.info = info
