@@ -282,6 +282,88 @@ int sg_warp_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_in, int wid
 		int nb_layers, uint16_t *d_out, int out_width, int out_height, const double *hom,
 		int interpolation, void *stream);
 
+/*
+ * Sequence preprocessing: replaces the loop body of seqpreprocess (src/core/siril.c:1019-1169):
+ * darkOptimization (:963-985), preprocess (:945-961: imoper SUB :150-187, fdiv :252-275) and
+ * cosmeticCorrection (src/algos/cosmetic_correction.c:275-294), on frames resident in HBM, in
+ * place.  Everything is exact integer / fp64 arithmetic written as the reference writes it, so
+ * the calibrated frames and the fitted dark scale equal the reference's bit for bit.
+ *
+ * Masters are host [C][H][W] memory-order images with the frames' nb_layers (the reference does
+ * not check this and reads absent planes); NULL = that master is not used (USE_OFFSET / USE_DARK /
+ * USE_FLAT of com.preprostatus).  They are taken as 16-bit images: an 8-bit master (whose
+ * statistics use a 256-bin histogram) is out of scope.
+ *   - `normalisation` is a float, as in struct preprocessing_data (src/core/siril.h:306-313);
+ *     autolevel sets it to (float) of the mean of the non-zero pixels of the flat's layer 0
+ *     (statistics() -> FnMeanSigma_ushort, src/algos/quantize.c:126-190).  A flat without a
+ *     non-zero pixel makes the reference give up: SG_ERR_GENERIC.
+ *   - dark_optimization (USE_OPTD): per frame a golden-section search of k in [0, 2] (13
+ *     iterations, goldenSectionSearch :922-943) minimising the background noise (the noise1 slot
+ *     of fits_img_stats_ushort, FnNoise1_ushort quantize.c:658-783, null value 0) of
+ *     max(raw - round_to_WORD(dark * k), 0) on layer 0.  A row whose sigma-clipped differences
+ *     give a negative variance (sum2 / n - mean * mean < 0: a NaN row) makes the reference's
+ *     qsort order undefined; such frames are unpinned.
+ *   - cosmetic (USE_COSME): the hot / cold pixels of the master dark (find_deviant_pixels
+ *     :176-240) are repaired in every frame, in the reference's list order, in place.  It applies
+ *     only to one-layer sequences; otherwise the reference logs and skips it, and so does this
+ *     (sg_prepro_info.cosmetic_applies = 0).  The dark's median is read from the reference's
+ *     histogram, whose 65536 bins cover [0, 65535): pixels of value 65535 fall outside and are not
+ *     counted, while they still count in the number of good pixels (src/gui/histogram.c:111-127).
+ *     PARITY-UNPINNED READ: for a cold pixel with all 24 neighbours inside the frame,
+ *     getMedian5x5 (:34-67) reads value[-1], one element before its heap block (undefined).  It
+ *     is taken as 0 here: that is what the n < 24 cases read by construction (a padding zero of
+ *     the calloc'ed array) and what glibc's chunk header holds in practice.  A deviant pixel
+ *     without any neighbour in the frame (a 1-pixel-wide or -high image) divides 0 by 0 in the
+ *     reference; it is set to 0 here.
+ * Refused with SG_ERR_GENERIC, nothing substituted: dark optimization with nb_layers != 1 (the
+ * reference extracts layer 0 into a one-layer image and then indexes layers 1 and 2 of it), dark
+ * optimization without a dark, cosmetic without a dark.  SG_ERR_SIZE: a dimension <= 0, or a
+ * plane of 2^31 pixels or more.
+ */
+typedef struct {
+	int width, height, nb_layers;
+	const uint16_t *offset, *dark, *flat;	/* host [C][H][W], or NULL */
+	int dark_optimization;	/* USE_OPTD */
+	int cosmetic;		/* USE_COSME */
+	double cosme_sigma[2];	/* args->sigma: {cold, hot}, -1 = that side off */
+	int is_cfa;		/* args->is_cfa: same-colour neighbours (step 2) */
+	int autolevel;		/* args->autolevel */
+	float normalisation;	/* args->normalisation (used when autolevel == 0) */
+} sg_prepro_desc;
+
+typedef struct {
+	double level;			/* the float level used by the flat division, as a double */
+	int64_t icold, ihot;		/* deviant pixels of the master dark */
+	double thres_cold, thres_hot;
+	double dark_sigma, dark_median;
+	int cosmetic_applies;		/* 0: not requested, or skipped (nb_layers != 1) */
+	/* schedule of the in-place correction: connected components of "lies in the other's
+	 * window", each walked in list order by one lane */
+	int64_t components, longest_component;
+} sg_prepro_info;
+
+typedef struct sg_prepro sg_prepro;
+
+/* all per-sequence work, once: derived masters uploaded to device `dev_index`, the level, the
+ * deviant list and its schedule */
+int sg_prepro_create(sg_ctx *ctx, int dev_index, const sg_prepro_desc *desc, sg_prepro **out);
+void sg_prepro_free(sg_prepro *pp);
+int sg_prepro_get_info(const sg_prepro *pp, sg_prepro_info *info);
+/* calibrate nframes resident frames in place: frame f, channel c, row r at
+ * d_frames[f*frame_stride + (c*height + r)*width] (frame_stride 0 = C*H*W; the layout of
+ * sg_frame_stats_ikss_device).  dark_k[nframes] (may be NULL) receives the fitted k of each frame
+ * ("Dark optimization: %.3lf"), 1.0 without dark optimization.  Synchronous. */
+int sg_prepro_frames_device(sg_ctx *ctx, int dev_index, sg_prepro *pp, uint16_t *d_frames, int nframes,
+		int64_t frame_stride, double *dark_k, void *stream);
+/* the same on host frames [nframes][C][H][W] (upload, run, download) on device 0 of the context
+ * (the prepro object must have been created there) */
+int sg_prepro_frames(sg_ctx *ctx, sg_prepro *pp, uint16_t *frames, int nframes, double *dark_k);
+/* the search's objective alone: noise[f] = evaluateNoiseOfCalibratedImage (:886-918) of frame f
+ * at k[f], i.e. the reference's bgnoise of max(raw - round_to_WORD(dark * k), 0) on layer 0; the
+ * frames are not changed.  Needs a dark. */
+int sg_prepro_noise_device(sg_ctx *ctx, int dev_index, sg_prepro *pp, const uint16_t *d_frames, int nframes,
+		int64_t frame_stride, const double *k, double *noise, void *stream);
+
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
  * (frame_stride 0 = nb_layers*height*width). */

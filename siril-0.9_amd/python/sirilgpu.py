@@ -71,6 +71,22 @@ class Rect(ctypes.Structure):
     _fields_ = [("x", ctypes.c_int), ("y", ctypes.c_int), ("w", ctypes.c_int), ("h", ctypes.c_int)]
 
 
+class PreproDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("nb_layers", ctypes.c_int),
+                ("offset", ctypes.c_void_p), ("dark", ctypes.c_void_p), ("flat", ctypes.c_void_p),
+                ("dark_optimization", ctypes.c_int), ("cosmetic", ctypes.c_int),
+                ("cosme_sigma", ctypes.c_double * 2), ("is_cfa", ctypes.c_int), ("autolevel", ctypes.c_int),
+                ("normalisation", ctypes.c_float)]
+
+
+class PreproInfo(ctypes.Structure):
+    _fields_ = [("level", ctypes.c_double), ("icold", ctypes.c_int64), ("ihot", ctypes.c_int64),
+                ("thres_cold", ctypes.c_double), ("thres_hot", ctypes.c_double),
+                ("dark_sigma", ctypes.c_double), ("dark_median", ctypes.c_double),
+                ("cosmetic_applies", ctypes.c_int), ("components", ctypes.c_int64),
+                ("longest_component", ctypes.c_int64)]
+
+
 READ_REGION_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(Rect))
 CONT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
@@ -90,7 +106,9 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_seq_read_frame", "sg_seq_load_device", "sg_seq_set_debayer", "sg_seq_set_debayer_method", "sg_warp_u16", "sg_warp_u16_device",
            "sg_frame_stats_ikss_device", "sg_compute_normalization", "sg_seqfile_read", "sg_seqfile_create",
            "sg_seqfile_free", "sg_seqfile_get_info", "sg_seqfile_get_images", "sg_seqfile_set_image",
-           "sg_seqfile_get_registration", "sg_seqfile_set_registration", "sg_seqfile_write"]
+           "sg_seqfile_get_registration", "sg_seqfile_set_registration", "sg_seqfile_write",
+           "sg_prepro_create", "sg_prepro_free", "sg_prepro_get_info", "sg_prepro_frames_device",
+           "sg_prepro_frames", "sg_prepro_noise_device"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -195,6 +213,18 @@ def load():
     lib.sg_warp_u16_device.argtypes = [P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.c_int,
                                        ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int, P]
     lib.sg_warp_u16_device.restype = ctypes.c_int
+    lib.sg_prepro_create.argtypes = [P, ctypes.c_int, ctypes.POINTER(PreproDesc), ctypes.POINTER(P)]
+    lib.sg_prepro_create.restype = ctypes.c_int
+    lib.sg_prepro_free.argtypes = [P]
+    lib.sg_prepro_free.restype = None
+    lib.sg_prepro_get_info.argtypes = [P, ctypes.POINTER(PreproInfo)]
+    lib.sg_prepro_get_info.restype = ctypes.c_int
+    lib.sg_prepro_frames_device.argtypes = [P, ctypes.c_int, P, P, ctypes.c_int, ctypes.c_int64, P, P]
+    lib.sg_prepro_frames_device.restype = ctypes.c_int
+    lib.sg_prepro_frames.argtypes = [P, P, P, ctypes.c_int, P]
+    lib.sg_prepro_frames.restype = ctypes.c_int
+    lib.sg_prepro_noise_device.argtypes = [P, ctypes.c_int, P, P, ctypes.c_int, ctypes.c_int64, P, P, P]
+    lib.sg_prepro_noise_device.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -607,12 +637,88 @@ class Context:
         self.check(rc, "sg_register_dft_u16_device" + ("_raw" if raw_quality else ""))
         return sx, sy, q
 
+    def prepro_frames_device(self, prepro, d_frames, nframes, frame_stride=0, want_k=True, stream=None, dev_index=0):
+        """seqpreprocess's loop body on resident frames, in place (sg_prepro_frames_device); returns
+        (rc, dark_k[nframes] or None)"""
+        k = np.zeros(nframes, dtype=np.float64) if want_k else None
+        rc = self.lib.sg_prepro_frames_device(self.ctx, dev_index, prepro.h, ctypes.c_void_p(d_frames), nframes,
+                                              frame_stride, k.ctypes.data_as(ctypes.c_void_p) if want_k else None,
+                                              ctypes.c_void_p(stream) if stream else None)
+        return rc, k
+
+    def prepro_frames_host(self, prepro, frames, want_k=True):
+        """the same on host frames [N][C][H][W], calibrated in place (sg_prepro_frames); returns (rc, dark_k)"""
+        assert frames.dtype == np.uint16 and frames.flags.c_contiguous and frames.flags.writeable
+        k = np.zeros(frames.shape[0], dtype=np.float64) if want_k else None
+        rc = self.lib.sg_prepro_frames(self.ctx, prepro.h, frames.ctypes.data_as(ctypes.c_void_p), frames.shape[0],
+                                       k.ctypes.data_as(ctypes.c_void_p) if want_k else None)
+        return rc, k
+
+    def prepro_noise_device(self, prepro, d_frames, nframes, k, frame_stride=0, stream=None, dev_index=0):
+        """the dark fit's objective of frame f at k[f] (sg_prepro_noise_device); returns (rc, noise[nframes])"""
+        k = np.ascontiguousarray(k, dtype=np.float64)
+        assert k.shape == (nframes,)
+        noise = np.zeros(nframes, dtype=np.float64)
+        rc = self.lib.sg_prepro_noise_device(self.ctx, dev_index, prepro.h, ctypes.c_void_p(d_frames), nframes,
+                                             frame_stride, k.ctypes.data_as(ctypes.c_void_p),
+                                             noise.ctypes.data_as(ctypes.c_void_p),
+                                             ctypes.c_void_p(stream) if stream else None)
+        return rc, noise
+
     def synth_fill(self, d_frames, nframes, C, H, W, row_begin, row_end, seed, maxshift, dev_index=0,
                    frame_stride=0, first_frame=0, plane_stride=0):
         rc = self.lib.sg_synth_fill_frames_device(self.ctx, dev_index, ctypes.c_void_p(d_frames), first_frame, nframes,
                                                   C, H, W, row_begin, row_end, seed, maxshift, frame_stride,
                                                   plane_stride, None)
         self.check(rc, "sg_synth_fill_frames_device")
+
+
+class Prepro:
+    """The per-sequence part of seqpreprocess (sg_prepro_create): masters [C][H][W] u16 or None."""
+
+    def __init__(self, ctx, width, height, nb_layers, offset=None, dark=None, flat=None, dark_optimization=False,
+                 cosmetic=False, cosme_sigma=(-1.0, -1.0), is_cfa=False, autolevel=False, normalisation=1.0,
+                 dev_index=0):
+        self.lib = ctx.lib
+        self.h = ctypes.c_void_p()
+        keep = []
+
+        def master(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.uint16)
+            assert a.size == nb_layers * height * width, "a master has the frames' shape"
+            keep.append(a)
+            return a.ctypes.data
+
+        d = PreproDesc()
+        d.width, d.height, d.nb_layers = width, height, nb_layers
+        d.offset, d.dark, d.flat = master(offset), master(dark), master(flat)
+        d.dark_optimization, d.cosmetic = int(dark_optimization), int(cosmetic)
+        d.cosme_sigma[0], d.cosme_sigma[1] = float(cosme_sigma[0]), float(cosme_sigma[1])
+        d.is_cfa, d.autolevel, d.normalisation = int(is_cfa), int(autolevel), float(normalisation)
+        self.rc = self.lib.sg_prepro_create(ctx.ctx, dev_index, ctypes.byref(d), ctypes.byref(self.h))
+        if self.rc != SG_OK:
+            self.h = None
+            raise RuntimeError(f"sg_prepro_create failed ({self.rc}): {ctx.error()}")
+
+    def info(self):
+        i = PreproInfo()
+        rc = self.lib.sg_prepro_get_info(self.h, ctypes.byref(i))
+        if rc != SG_OK:
+            raise RuntimeError(f"sg_prepro_get_info failed ({rc})")
+        return i
+
+    def close(self):
+        if self.h:
+            self.lib.sg_prepro_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def compute_normalization(mode, location, scale, ref_image=0):
