@@ -364,6 +364,78 @@ int sg_prepro_frames(sg_ctx *ctx, sg_prepro *pp, uint16_t *frames, int nframes, 
 int sg_prepro_noise_device(sg_ctx *ctx, int dev_index, sg_prepro *pp, const uint16_t *d_frames, int nframes,
 		int64_t frame_stride, const double *k, double *noise, void *stream);
 
+/*
+ * Star candidates: the whole-image part of peaker (src/algos/star_finder.c:103-255), which
+ * register_star_alignment calls once per frame (src/registration/registration.c:583-586, :682),
+ * on frames resident in HBM.  Integer, fp32 and fp64 arithmetic in the reference's order, so the
+ * records, the detection plane, the candidate list and the boxes equal the reference's bit for bit.
+ *   1. Threshold (Compute_threshold :39-57): statistics(fit, layer, NULL, STATS_BASIC,
+ *      STATS_ZERO_NULLCHECK): ngood = the non-zero pixels, sigma from FnMeanSigma_ushort's
+ *      sequential double sums, median from computeHisto's 65536 bins over [0, 65535) (65535 is not
+ *      binned but counts in ngood; from bin 1, the first bin whose running count exceeds
+ *      ngood * 0.5, else 0).  threshold = (WORD)((WORD)median + sigma_k * (WORD)sigma), norm =
+ *      65535, bg = median.
+ *   2. Detection plane (get_wavelet_layers(.., 3, 2, TO_PAVE_BSPLINE, layer),
+ *      src/core/siril.c:1285-1336): pave_2d_bspline_smooth with Step 1, then Step 2
+ *      (src/algos/pave.c:227-284) of (float)image, indices clamped, operand order kept, quantised
+ *      by reget_rawdata (src/algos/reconstr.c:120-140).
+ *   3. Peak test (:176-199) in display (top-down) coordinates over y in [aY0 + r, aY1 - r),
+ *      x in [aX0 + r, aX1 - r): p > threshold, p < norm, no greater 8-neighbour, no equal
+ *      neighbour in the row above or to the left.  Candidates in raster order (y outer, x inner).
+ *   4. Boxes (:203-211): the 2r x 2r pixels of the ORIGINAL image around a candidate in gsl_matrix
+ *      order, boxes[ii * 2r + jj] = top[y - r + jj][x - r + ii], as uint16_t.
+ * Kept quirks, each reported per frame:
+ *   - min(width, height) < 32: wavelet_transform_data refuses (src/algos/transform.c:194-201),
+ *     peaker ignores it, and the detection plane is the unsmoothed image (wavelet_applied = 0);
+ *   - a frame without a non-zero pixel: statistics() returns NULL and the reference goes on with an
+ *     uninitialised norm and bg; here such a frame has no candidate (no_data = 1), the call succeeds;
+ *   - PARITY-UNPINNED: a threshold of 65536 or more is undefined in C; the x86-64 result (truncated
+ *     to int32, low 16 bits) is taken and threshold_wrapped = 1;
+ *   - reget_rawdata rescales a plane whose float maximum exceeds 65535 (ratio_applied = 1; no
+ *     input reaches it);
+ *   - sigma_on_host = 1: the frame's sum of squares reached 2^53, where the reference's double
+ *     sums round, and the plane was summed sequentially on the host.
+ * Refused before any device work: SG_ERR_SIZE for a dimension <= 0, a plane of 2^31 pixels or
+ * more, layer outside [0, nb_layers), an area not inside the image (the reference reads out of
+ * bounds); SG_ERR_GENERIC for radius < 1 (the 3x3 test would leave the image), sigma negative or
+ * not finite, max_candidates < 0.  2 * radius >= a side of the area is no error: no candidate.
+ * Left to the caller: the PSF fit (psf_global_minimisation(z, bg = median, layer, FALSE, FALSE),
+ * GSL, unpinned) with xpos = x + x0 - r - 1, ypos = y + y0 - r - 1 (:221-222), is_star, the
+ * MAX_STARS cap on accepted stars (the reference has no cap on candidates), sort_stars and the
+ * matching (new_star_match); see INTEGRATION.md.
+ */
+typedef struct {
+	int width, height, nb_layers;
+	int layer;
+	int radius;		/* sf->radius */
+	double sigma;		/* sf->sigma, the k of the threshold */
+	int use_area;
+	sg_rect area;		/* display (top-down) coordinates, used when use_area != 0 */
+	int max_candidates;	/* capacity of cand_xy / boxes per frame */
+} sg_findstar_desc;
+
+typedef struct {
+	int64_t ngood;
+	double median, sigma;
+	int threshold;
+	int64_t ncand;		/* candidates found */
+	int64_t nstored;	/* min(ncand, max_candidates): the first ones in raster order */
+	int wavelet_applied, ratio_applied, sigma_on_host, threshold_wrapped, no_data;
+} sg_findstar_frame;
+
+/* frames: frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
+ * (frame_stride 0 = C*H*W; the layout of sg_prepro_frames_device); never written.
+ * per_frame[nframes]; cand_xy: host [nframes][max_candidates][2] int32, (x, y) in display
+ * coordinates; boxes: host [nframes][max_candidates][2r * 2r] uint16, may be NULL; d_wave: device
+ * [nframes][H][W], memory order, receives the detection plane, may be NULL.  Synchronous. */
+int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_desc *desc, const uint16_t *d_frames,
+		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes,
+		uint16_t *d_wave, void *stream);
+/* the same on host frames [nframes][C][H][W] on device 0 of the context; wave: host
+ * [nframes][H][W], may be NULL */
+int sg_findstar(sg_ctx *ctx, const sg_findstar_desc *desc, const uint16_t *frames, int nframes,
+		sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes, uint16_t *wave);
+
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
  * (frame_stride 0 = nb_layers*height*width). */

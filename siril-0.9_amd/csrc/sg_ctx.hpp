@@ -102,6 +102,9 @@ struct SgDevice {
 	SgBuf io_raw, io_bad;
 	SgBuf warp_tab;		/* sg_warp.hip interpolation table */
 	int warp_tab_interp = -1;
+	/* star candidates (sg_findstar.hip): histograms / records / masks / row offsets, the scratch
+	 * detection plane, the candidate list and boxes, host frames of sg_findstar */
+	SgBuf fs_work, fs_plane, fs_out, fs_frames;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };

@@ -87,6 +87,19 @@ class PreproInfo(ctypes.Structure):
                 ("longest_component", ctypes.c_int64)]
 
 
+class FindstarDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("nb_layers", ctypes.c_int),
+                ("layer", ctypes.c_int), ("radius", ctypes.c_int), ("sigma", ctypes.c_double),
+                ("use_area", ctypes.c_int), ("area", Rect), ("max_candidates", ctypes.c_int)]
+
+
+class FindstarFrame(ctypes.Structure):
+    _fields_ = [("ngood", ctypes.c_int64), ("median", ctypes.c_double), ("sigma", ctypes.c_double),
+                ("threshold", ctypes.c_int), ("ncand", ctypes.c_int64), ("nstored", ctypes.c_int64),
+                ("wavelet_applied", ctypes.c_int), ("ratio_applied", ctypes.c_int),
+                ("sigma_on_host", ctypes.c_int), ("threshold_wrapped", ctypes.c_int), ("no_data", ctypes.c_int)]
+
+
 READ_REGION_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(Rect))
 CONT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
@@ -108,7 +121,7 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_seqfile_free", "sg_seqfile_get_info", "sg_seqfile_get_images", "sg_seqfile_set_image",
            "sg_seqfile_get_registration", "sg_seqfile_set_registration", "sg_seqfile_write",
            "sg_prepro_create", "sg_prepro_free", "sg_prepro_get_info", "sg_prepro_frames_device",
-           "sg_prepro_frames", "sg_prepro_noise_device"]
+           "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -225,6 +238,11 @@ def load():
     lib.sg_prepro_frames.restype = ctypes.c_int
     lib.sg_prepro_noise_device.argtypes = [P, ctypes.c_int, P, P, ctypes.c_int, ctypes.c_int64, P, P, P]
     lib.sg_prepro_noise_device.restype = ctypes.c_int
+    lib.sg_findstar_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(FindstarDesc), P, ctypes.c_int, ctypes.c_int64,
+                                       ctypes.POINTER(FindstarFrame), P, P, P, P]
+    lib.sg_findstar_device.restype = ctypes.c_int
+    lib.sg_findstar.argtypes = [P, ctypes.POINTER(FindstarDesc), P, ctypes.c_int, ctypes.POINTER(FindstarFrame), P, P, P]
+    lib.sg_findstar.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -441,6 +459,23 @@ def make_desc(method, N, W, H, C, rejection=NO_REJEC, normalize=NO_NORM, sig=(4.
     if resident_rows is not None:
         d.resident_rows[0], d.resident_rows[1] = int(resident_rows[0]), int(resident_rows[1])
     return d, keep
+
+
+def make_findstar_desc(W, H, C, layer, radius, sigma, area=None, max_candidates=2000):
+    d = FindstarDesc()
+    d.width, d.height, d.nb_layers, d.layer = W, H, C, layer
+    d.radius, d.sigma, d.max_candidates = radius, sigma, max_candidates
+    d.use_area = 0 if area is None else 1
+    if area is not None:
+        d.area.x, d.area.y, d.area.w, d.area.h = [int(v) for v in area]
+    return d
+
+
+def _findstar_arrays(nframes, radius, max_candidates, want_boxes):
+    n, m, r2 = max(nframes, 0), max(max_candidates, 0), 2 * max(radius, 0)
+    xy = np.zeros((n, m, 2), dtype=np.int32)
+    bx = np.zeros((n, m, r2, r2), dtype=np.uint16) if want_boxes else None
+    return xy, bx
 
 
 class Context:
@@ -664,6 +699,38 @@ class Context:
                                              noise.ctypes.data_as(ctypes.c_void_p),
                                              ctypes.c_void_p(stream) if stream else None)
         return rc, noise
+
+    def findstar_device(self, d_frames, nframes, C, H, W, radius, sigma, layer=0, area=None, max_candidates=2000,
+                        want_boxes=True, d_wave=None, frame_stride=0, stream=None, dev_index=0):
+        """peaker's whole-image part on resident frames (sg_findstar_device).  area = (x, y, w, h) in display
+        coordinates or None; d_wave = a device pointer for the detection planes [nframes][H][W] or None.
+        Returns (rc, records, cand_xy[nframes][max][2] int32, boxes[nframes][max][2r][2r] uint16 or None);
+        records is a list of FindstarFrame, boxes[f][i][ii][jj] is the gsl_matrix element (ii, jj)."""
+        d = make_findstar_desc(W, H, C, layer, radius, sigma, area, max_candidates)
+        rec = (FindstarFrame * max(nframes, 1))()
+        xy, bx = _findstar_arrays(nframes, radius, max_candidates, want_boxes)
+        rc = self.lib.sg_findstar_device(self.ctx, dev_index, ctypes.byref(d), ctypes.c_void_p(d_frames), nframes,
+                                         frame_stride, rec, xy.ctypes.data_as(ctypes.c_void_p),
+                                         bx.ctypes.data_as(ctypes.c_void_p) if want_boxes else None,
+                                         ctypes.c_void_p(d_wave) if d_wave else None,
+                                         ctypes.c_void_p(stream) if stream else None)
+        return rc, list(rec)[:max(nframes, 0)], xy, bx
+
+    def findstar(self, frames, radius, sigma, layer=0, area=None, max_candidates=2000, want_boxes=True,
+                 want_wave=False):
+        """the same on host frames [N][C][H][W] u16 (sg_findstar); returns (rc, records, cand_xy, boxes or None,
+        wave[N][H][W] or None)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        N, C, H, W = frames.shape
+        d = make_findstar_desc(W, H, C, layer, radius, sigma, area, max_candidates)
+        rec = (FindstarFrame * max(N, 1))()
+        xy, bx = _findstar_arrays(N, radius, max_candidates, want_boxes)
+        wave = np.zeros((N, H, W), dtype=np.uint16) if want_wave else None
+        rc = self.lib.sg_findstar(self.ctx, ctypes.byref(d), frames.ctypes.data_as(ctypes.c_void_p), N, rec,
+                                  xy.ctypes.data_as(ctypes.c_void_p),
+                                  bx.ctypes.data_as(ctypes.c_void_p) if want_boxes else None,
+                                  wave.ctypes.data_as(ctypes.c_void_p) if want_wave else None)
+        return rc, list(rec)[:N], xy, bx, wave
 
     def synth_fill(self, d_frames, nframes, C, H, W, row_begin, row_end, seed, maxshift, dev_index=0,
                    frame_stride=0, first_frame=0, plane_stride=0):
