@@ -436,6 +436,79 @@ int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_desc *desc,
 int sg_findstar(sg_ctx *ctx, const sg_findstar_desc *desc, const uint16_t *frames, int nframes,
 		sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes, uint16_t *wave);
 
+/*
+ * Fitted stars: all of peaker (src/algos/star_finder.c:103-255) for resident frames.  After the
+ * candidates of sg_findstar*, each stored candidate's 2r x 2r box is fitted on the device
+ * (psf_global_minimisation(z, bg = median, layer, FALSE, FALSE), src/algos/PSF.c:46-157, 160-220,
+ * 314-428, 620-662): the start values of psf_init_data bit for bit, then GSL's lmsder on
+ * psf_Gaussian_f / _df restated in fp64 (siril-0.9_amd/csrc/sg_psf.h, DESIGN.md §6: PARITY-UNPINNED
+ * against any one GSL build, checked against tests/psf_ref.py within a measured tolerance), the
+ * finish, psf_update_units as the two factors fwhm_scale_x / _y, is_star, xpos = x + x0 - r - 1 and
+ * ypos = y + y0 - r - 1.  The boxes never leave the device.  Per frame the accepted stars are the
+ * first max_stars in raster (candidate) order, returned sorted ascending by mag, ties by cand (the
+ * reference's qsort leaves ties open and its OpenMP order depends on timing; the serial order is
+ * the contract).  Kept quirks: the box is transposed (matrix rows run along image x, x0 belongs to
+ * image y) and xpos / ypos are taken literally; a half-maximum walk that does not move gives S = 0,
+ * a fit that is not finite, SG_FIT_NONFINITE.  Departures: rmse is taken at the final x (the
+ * reference reports the solver's last model evaluation, which may be a refused trial step); the
+ * relative uncertainties are not computed (the reference does not use them).
+ * Refused before any device work, beyond what sg_findstar refuses: SG_ERR_GENERIC for radius > 32,
+ * roundness or a scale not finite, norm not 255 or 65535, max_stars outside [0, 50000].
+ * radius = 1 is no error: every candidate gets SG_FIT_NOT_ENOUGH_PIXELS.
+ * Left to the caller: the matching (new_star_match), FWHM_average, the angle fit, the
+ * uncertainties, 8-bit frames.
+ */
+#define SG_STARFIT_MAX_RADIUS 32
+#define SG_STARFIT_MAX_STARS 50000	/* MAX_STARS */
+
+enum {
+	SG_FIT_STAR = 0,
+	SG_FIT_NOT_ENOUGH_PIXELS = 1,	/* n <= 6 */
+	SG_FIT_NONFINITE = 2,
+	SG_FIT_BAD_FWHM = 3,		/* FWHM not finite or <= 0 */
+	SG_FIT_NOT_STAR = 4,		/* is_star refused it: failed_test says where */
+	SG_FIT_OVER_CAP = 5		/* a star beyond the first max_stars */
+};
+
+typedef struct {
+	sg_findstar_desc find;
+	double roundness;	/* sf->roundness */
+	double norm;		/* get_normalized_value(&gfit): 255 or 65535, of the DISPLAYED image */
+	double fwhm_scale_x, fwhm_scale_y;	/* psf_update_units' factors; 1.0 while the units stay pixels */
+	int max_stars;		/* capacity of stars per frame, at most SG_STARFIT_MAX_STARS */
+	int want_candidates;	/* fill cands */
+} sg_starfit_desc;
+
+/* an accepted star; B, A and rmse are normalised, sx >= sy, fwhm in the scaled units */
+typedef struct {
+	int32_t cand;		/* index in the frame's candidate list */
+	int32_t x, y;		/* the candidate, display coordinates */
+	int32_t iters;		/* outer iterations of the solver */
+	double B, A, x0, y0, sx, sy, fwhmx, fwhmy, mag, rmse, xpos, ypos;
+} sg_star;
+
+/* every stored candidate, for diagnosis */
+typedef struct {
+	int32_t x, y;
+	int32_t iters;
+	int32_t status;		/* SG_FIT_* */
+	int32_t failed_test;	/* SG_FIT_NOT_STAR: 1 .. 8, the test of is_star (:60-75) that failed */
+	int32_t reserved;
+	double init[6];		/* the start values B, A, x0, y0, SX, SY */
+	double B, A, x0, y0, sx, sy, fwhmx, fwhmy, mag, rmse, xpos, ypos;
+} sg_starfit_cand;
+
+/* frames as in sg_findstar_device.  per_frame[nframes]; nstars: host [nframes] int32; stars: host
+ * [nframes][max_stars], the first nstars[f] of frame f written; cands: host
+ * [nframes][find.max_candidates], the first nstored written, NULL unless want_candidates.
+ * Synchronous. */
+int sg_findstar_fit_device(sg_ctx *ctx, int dev_index, const sg_starfit_desc *desc, const uint16_t *d_frames,
+		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars,
+		sg_starfit_cand *cands, void *stream);
+/* the same on host frames [nframes][C][H][W] on device 0 of the context */
+int sg_findstar_fit(sg_ctx *ctx, const sg_starfit_desc *desc, const uint16_t *frames, int nframes,
+		sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars, sg_starfit_cand *cands);
+
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
  * (frame_stride 0 = nb_layers*height*width). */

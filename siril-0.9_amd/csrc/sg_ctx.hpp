@@ -104,7 +104,7 @@ struct SgDevice {
 	int warp_tab_interp = -1;
 	/* star candidates (sg_findstar.hip): histograms / records / masks / row offsets, the scratch
 	 * detection plane, the candidate list and boxes, host frames of sg_findstar */
-	SgBuf fs_work, fs_plane, fs_out, fs_frames;
+	SgBuf fs_work, fs_plane, fs_out, fs_frames, fs_fit;	/* fs_fit: the fit records of sg_findstar_fit* */
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };

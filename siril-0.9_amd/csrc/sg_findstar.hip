@@ -16,11 +16,24 @@
  *     the candidates written at row offset + rank inside the row, which is the raster order of the
  *     reference's single-thread loop, the first `capacity` of them kept.
  *   - k_findstar_boxes: one wave per stored candidate gathers its 2r x 2r box of the original image.
+ * Fitted stars (sg_findstar_fit*), the second half of peaker, on the candidate list k_findstar_emit
+ * leaves on the device:
+ *   - k_starfit_fit: one wave per stored candidate.  Its box goes into LDS as u16, pixels strided
+ *     over the 64 lanes; each lane sums its share of J^T J, J^T f and |f|^2 in fp64 (one exp per
+ *     pixel and evaluation), a butterfly of fixed order adds the lanes, so every lane holds the same
+ *     bits and runs the 6 x 6 solver of sg_psf.h redundantly with uniform branches.  Lane 0 writes
+ *     the candidate's record with its status (is_star included).
+ *   - k_starfit_select: one wave per frame scans the statuses in candidate order, keeps the first
+ *     max_stars accepted as compact sg_star records and marks the rest SG_FIT_OVER_CAP.
+ *   The host downloads the stars (and the candidate records when asked) and sorts each frame's
+ *   stars by (mag, cand).
  * The frames are only read.
  */
 #include "sg_common.hpp"
 #include "sg_ctx.hpp"
 #include "sg_findstar_plan.hpp"
+#include "sg_starfit_plan.hpp"
+#include "sg_psf.h"
 #include <algorithm>
 #include <vector>
 
@@ -260,21 +273,190 @@ __global__ void __launch_bounds__(256) k_findstar_boxes(SgPeakParams p) {
 	}
 }
 
+struct SgFitParams {
+	const uint16_t *img;	/* the layer of the chunk's first frame */
+	int64_t fstride;
+	int W, H, r, max_stars;
+	const unsigned long long *nst, *base;	/* [nf] stored candidates, first entry in xy / cands / stars */
+	const int *xy;
+	const double *bg;	/* [nf] the frame's median */
+	double norm, scale_x, scale_y, roundness;
+	sg_starfit_cand *cands;
+	sg_star *stars;
+	int *nstars;		/* [nf] */
+};
+
+/* the lanes' values added in a fixed order; every lane receives the same bits (IEEE addition
+ * commutes, and each level adds the same two partial sums in both partner lanes) */
+__device__ static inline double sgs_wave_sum(double v) {
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1)
+		v += __shfl_xor(v, o, 64);
+	return v;
+}
+
+/* the evaluator of sgp_lm over a box in LDS: pixel p = i * n2 + j belongs to lane p % 64 */
+struct SgPsfWaveEval {
+	const uint16_t *box;
+	int n2, ne, lane;
+	__device__ void full(const double x[SGP_NP], SgPsfSums &s) const {
+		sgp_sums_zero(s);
+		for (int p = lane; p < ne; p += 64) {
+			const int i = p / n2, j = p - i * n2;
+			sgp_pixel(x, (double)(j + 1), (double)(i + 1), (double)box[p], s);
+		}
+#pragma unroll
+		for (int k = 0; k < 21; k++)
+			s.a[k] = sgs_wave_sum(s.a[k]);
+#pragma unroll
+		for (int k = 0; k < SGP_NP; k++)
+			s.g[k] = sgs_wave_sum(s.g[k]);
+		s.ff = sgs_wave_sum(s.ff);
+	}
+	__device__ double resid(const double x[SGP_NP]) const {
+		double ff = 0.;
+		for (int p = lane; p < ne; p += 64) {
+			const int i = p / n2, j = p - i * n2;
+			const double r = sgp_resid(x, (double)(j + 1), (double)(i + 1), (double)box[p]);
+			ff += r * r;
+		}
+		return sgs_wave_sum(ff);
+	}
+	__device__ double flux(double B) const {
+		double t = 0.;
+		for (int p = lane; p < ne; p += 64)
+			t += (double)box[p] - B;
+		return sgs_wave_sum(t);
+	}
+};
+
+/* waves per SIMD the fit kernel is compiled for (A/B: make EXTRA=-DSGS_OCC=n).  The solver's
+ * dependent fp64 chains want a second wave to hide behind; a third or fourth costs more in
+ * spills than it hides (profiles/starfit_64x4096.log). */
+#ifndef SGS_OCC
+#define SGS_OCC 2
+#endif
+#define SGS_OCC_ATTR __attribute__((amdgpu_waves_per_eu(SGS_OCC, SGS_OCC)))
+
+/* one wave per stored candidate: box -> LDS, start values, fit, finish, is_star, record.  The scan
+ * rectangle keeps the box inside the area, so every read is inside the image. */
+__global__ void __launch_bounds__(64 * SGS_WAVES) SGS_OCC_ATTR k_starfit_fit(SgFitParams p) {
+	extern __shared__ uint16_t s_box[];	/* SGS_WAVES boxes */
+	const int f = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const unsigned long long ci = (unsigned long long)blockIdx.x * SGS_WAVES + wv;
+	const bool active = ci < p.nst[f];
+	const int n2 = 2 * p.r, ne = n2 * n2;
+	uint16_t *box = s_box + wv * ne;
+	unsigned long long g = 0;
+	int cx = 0, cy = 0;
+	if (active) {
+		g = p.base[f] + ci;
+		cx = p.xy[2 * g];
+		cy = p.xy[2 * g + 1];
+		const uint16_t *img = p.img + (int64_t)f * p.fstride;
+		for (int q = lane; q < ne; q += 64) {	/* box[ii * n2 + jj] = top[cy - r + jj][cx - r + ii] */
+			const int ii = q / n2, jj = q - ii * n2;
+			box[q] = img[(int64_t)(p.H - 1 - (cy - p.r + jj)) * p.W + (cx - p.r + ii)];
+		}
+	}
+	__syncthreads();
+	if (!active)
+		return;
+	/* removeHotPixels and the first maximum in row-major order: the key orders by value, then by
+	 * the smaller index (ne <= 4096) */
+	uint32_t key = 0;
+	for (int q = lane; q < ne; q += 64) {
+		const int i = q / n2, j = q - i * n2;
+		const uint32_t k = ((uint32_t)sgp_median3x3(box, n2, i, j) << 16) | (uint32_t)(65535 - q);
+		key = k > key ? k : key;
+	}
+#pragma unroll
+	for (int o = 32; o >= 1; o >>= 1) {
+		const uint32_t u = (uint32_t)__shfl_xor((int)key, o, 64);
+		key = u > key ? u : key;
+	}
+	const int best = 65535 - (int)(key & 0xFFFFu);
+	double init[SGP_NP];
+	sgp_init_walks(box, n2, p.bg[f], best / n2, best % n2, (uint16_t)(key >> 16), init);
+	SgPsfWaveEval ev = {box, n2, ne, lane};
+	SgPsfFit o;
+	sgp_fit(ev, init, n2, cx, cy, p.norm, p.scale_x, p.scale_y, p.roundness, o);
+	if (lane == 0) {
+		sg_starfit_cand c;
+		c.x = cx;
+		c.y = cy;
+		c.iters = o.iters;
+		c.status = o.status;
+		c.failed_test = o.failed_test;
+		c.reserved = 0;
+		for (int k = 0; k < SGP_NP; k++)
+			c.init[k] = init[k];
+		c.B = o.B;
+		c.A = o.A;
+		c.x0 = o.x0;
+		c.y0 = o.y0;
+		c.sx = o.sx;
+		c.sy = o.sy;
+		c.fwhmx = o.fwhmx;
+		c.fwhmy = o.fwhmy;
+		c.mag = o.mag;
+		c.rmse = o.rmse;
+		c.xpos = o.xpos;
+		c.ypos = o.ypos;
+		p.cands[g] = c;
+	}
+}
+
+/* one wave per frame: the first max_stars accepted candidates in candidate order -> stars[base + rank],
+ * the accepted ones beyond them marked SG_FIT_OVER_CAP, nstars[f] */
+__global__ void __launch_bounds__(64) k_starfit_select(SgFitParams p) {
+	const int f = blockIdx.x, lane = threadIdx.x;
+	const unsigned long long n = p.nst[f], base = p.base[f];
+	unsigned long long run = 0;
+	for (unsigned long long c0 = 0; c0 < n; c0 += 64) {
+		const unsigned long long c = c0 + lane;
+		const bool acc = c < n && p.cands[base + c].status == SG_FIT_STAR;
+		const unsigned long long b = __ballot(acc);
+		const unsigned long long rank = run + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+		if (acc) {
+			sg_starfit_cand &q = p.cands[base + c];
+			if (rank < (unsigned long long)p.max_stars) {
+				sg_star st;
+				st.cand = (int32_t)c;
+				st.x = q.x;
+				st.y = q.y;
+				st.iters = q.iters;
+				st.B = q.B;
+				st.A = q.A;
+				st.x0 = q.x0;
+				st.y0 = q.y0;
+				st.sx = q.sx;
+				st.sy = q.sy;
+				st.fwhmx = q.fwhmx;
+				st.fwhmy = q.fwhmy;
+				st.mag = q.mag;
+				st.rmse = q.rmse;
+				st.xpos = q.xpos;
+				st.ypos = q.ypos;
+				p.stars[base + rank] = st;
+			} else
+				q.status = SG_FIT_OVER_CAP;
+		}
+		run += (unsigned long long)__popcll(b);
+	}
+	if (lane == 0)
+		p.nstars[f] = (int)(run < (unsigned long long)p.max_stars ? run : (unsigned long long)p.max_stars);
+}
+
 static inline size_t sgf_up16(size_t v) {
 	return (v + 15) & ~(size_t)15;
 }
 
-extern "C" int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_desc *desc, const uint16_t *d_frames,
-		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes,
-		uint16_t *d_wave, void *stream) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
-		return SG_ERR_GENERIC;
-	SgFindstarPlan pl;
-	int rc = sg_findstar_plan(desc, pl);
-	if (rc != SG_OK)
-		return set_err(ctx, rc, "%s", pl.err);
-	if (!d_frames || nframes < 1 || !per_frame || frame_stride < 0 || (pl.max_candidates > 0 && !cand_xy))
-		return set_err(ctx, SG_ERR_GENERIC, "findstar: missing frames, records or candidate array%s", "");
+/* the body of sg_findstar_device; with a fit plan `fp` it goes on, chunk by chunk, to the fit of the
+ * stored candidates (nstars, stars, cands of sg_findstar_fit_device; cand_xy and boxes are NULL) */
+static int sgf_run(sg_ctx *ctx, int dev_index, const SgFindstarPlan &pl, const uint16_t *d_frames, int nframes,
+		int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes, uint16_t *d_wave,
+		void *stream, const SgStarfitPlan *fp, int32_t *nstars, sg_star *stars, sg_starfit_cand *cands) {
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
 	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
@@ -303,7 +485,10 @@ extern "C" int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_
 	std::vector<uint64_t> hstat(4 * (size_t)chunk), hnst(2 * (size_t)chunk);
 	std::vector<uint32_t> hfmax(chunk), htot(chunk);
 	std::vector<int> hthr(chunk);
+	std::vector<double> hmed(chunk);
 	std::vector<uint16_t> hplane;
+	if (fp)
+		memset(nstars, 0, sizeof(int32_t) * nframes);
 	for (int f0 = 0; f0 < nframes; f0 += chunk) {
 		const int nf = std::min(nframes - f0, chunk);
 		const uint16_t *lay = d_frames + (int64_t)f0 * frame_stride + (int64_t)pl.layer * npix;
@@ -427,7 +612,7 @@ extern "C" int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_
 			HIPCHK(hipGetLastError());
 		}
 		/* each frame's stored entries straight into the caller's arrays */
-		for (int f = 0; f < nf; f++) {
+		for (int f = 0; f < nf && cand_xy; f++) {
 			const size_t at = hnst[nf + f], n = hnst[f], slot = (size_t)(f0 + f) * pl.max_candidates;
 			if (!n)
 				continue;
@@ -436,7 +621,125 @@ extern "C" int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_
 				HIPCHK(hipMemcpyAsync(boxes + slot * (size_t)pl.box_elems, kp.boxes + at * (size_t)pl.box_elems,
 						n * (size_t)pl.box_elems * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
 		}
+		if (fp) {
+			/* the chunk's fit block: medians, star counts, candidate records, compact stars */
+			const size_t o_bg = 0, o_ns = o_bg + sgf_up16(sizeof(double) * nf), o_cd = o_ns + sgf_up16(sizeof(int) * nf);
+			const size_t o_st = o_cd + sgf_up16(total * sizeof(sg_starfit_cand));
+			HIPCHK(ensure(dv.fs_fit, o_st + sgf_up16(total * sizeof(sg_star))));
+			char *fb = (char *)dv.fs_fit.p;
+			for (int f = 0; f < nf; f++)
+				hmed[f] = rec[f].median;
+			HIPCHK(hipMemcpyAsync(fb + o_bg, hmed.data(), sizeof(double) * nf, hipMemcpyHostToDevice, s));
+			SgFitParams q;
+			q.img = lay;
+			q.fstride = frame_stride;
+			q.W = W;
+			q.H = H;
+			q.r = pl.r;
+			q.max_stars = fp->max_stars;
+			q.nst = nst;
+			q.base = nst + nf;
+			q.xy = kp.xy;
+			q.bg = (const double *)(fb + o_bg);
+			q.norm = fp->norm;
+			q.scale_x = fp->scale_x;
+			q.scale_y = fp->scale_y;
+			q.roundness = fp->roundness;
+			q.cands = (sg_starfit_cand *)(fb + o_cd);
+			q.stars = (sg_star *)(fb + o_st);
+			q.nstars = (int *)(fb + o_ns);
+			hipLaunchKernelGGL(k_starfit_fit, dim3(sgs_grid_x(most), (unsigned)nf), dim3(64 * SGS_WAVES), fp->lds_bytes, s, q);
+			HIPCHK(hipGetLastError());
+			hipLaunchKernelGGL(k_starfit_select, dim3((unsigned)nf), dim3(64), 0, s, q);
+			HIPCHK(hipGetLastError());
+			HIPCHK(hipMemcpyAsync(nstars + f0, q.nstars, sizeof(int) * nf, hipMemcpyDeviceToHost, s));
+			HIPCHK(hipStreamSynchronize(s));
+			for (int f = 0; f < nf; f++) {
+				const size_t at = hnst[nf + f], n = hnst[f];
+				if (nstars[f0 + f] > 0)
+					HIPCHK(hipMemcpyAsync(stars + (size_t)(f0 + f) * fp->max_stars, q.stars + at,
+							(size_t)nstars[f0 + f] * sizeof(sg_star), hipMemcpyDeviceToHost, s));
+				if (cands && n)
+					HIPCHK(hipMemcpyAsync(cands + (size_t)(f0 + f) * pl.max_candidates, q.cands + at,
+							n * sizeof(sg_starfit_cand), hipMemcpyDeviceToHost, s));
+			}
+		}
 		HIPCHK(hipStreamSynchronize(s));
+		for (int f = 0; fp && f < nf; f++) {	/* sort_stars: ascending mag; ties by candidate (the serial order) */
+			sg_star *b = stars + (size_t)(f0 + f) * fp->max_stars;
+			std::sort(b, b + nstars[f0 + f], [](const sg_star &u, const sg_star &v) {
+				return u.mag < v.mag || (u.mag == v.mag && u.cand < v.cand);
+			});
+		}
+	}
+	return SG_OK;
+}
+
+extern "C" int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_desc *desc, const uint16_t *d_frames,
+		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes,
+		uint16_t *d_wave, void *stream) {
+	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+		return SG_ERR_GENERIC;
+	SgFindstarPlan pl;
+	int rc = sg_findstar_plan(desc, pl);
+	if (rc != SG_OK)
+		return set_err(ctx, rc, "%s", pl.err);
+	if (!d_frames || nframes < 1 || !per_frame || frame_stride < 0 || (pl.max_candidates > 0 && !cand_xy))
+		return set_err(ctx, SG_ERR_GENERIC, "findstar: missing frames, records or candidate array%s", "");
+	return sgf_run(ctx, dev_index, pl, d_frames, nframes, frame_stride, per_frame, cand_xy, boxes, d_wave, stream, nullptr,
+			nullptr, nullptr, nullptr);
+}
+
+static int sgs_check(sg_ctx *ctx, const sg_starfit_desc *desc, SgStarfitPlan &fp, const void *frames, int nframes,
+		const sg_findstar_frame *per_frame, const int32_t *nstars, const sg_star *stars, const sg_starfit_cand *cands) {
+	const int rc = sg_starfit_plan(desc, fp);
+	if (rc != SG_OK)
+		return set_err(ctx, rc, "%s", fp.err);
+	if (!frames || nframes < 1 || !per_frame || !nstars || (fp.max_stars > 0 && !stars) ||
+			(fp.want_candidates && fp.find.max_candidates > 0 && !cands))
+		return set_err(ctx, SG_ERR_GENERIC, "starfit: missing frames, records, star or candidate array%s", "");
+	return SG_OK;
+}
+
+extern "C" int sg_findstar_fit_device(sg_ctx *ctx, int dev_index, const sg_starfit_desc *desc, const uint16_t *d_frames,
+		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars,
+		sg_starfit_cand *cands, void *stream) {
+	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+		return SG_ERR_GENERIC;
+	SgStarfitPlan fp;
+	const int rc = sgs_check(ctx, desc, fp, d_frames, nframes, per_frame, nstars, stars, cands);
+	if (rc != SG_OK)
+		return rc;
+	if (frame_stride < 0)
+		return set_err(ctx, SG_ERR_GENERIC, "starfit: negative frame stride%s", "");
+	return sgf_run(ctx, dev_index, fp.find, d_frames, nframes, frame_stride, per_frame, nullptr, nullptr, nullptr, stream,
+			&fp, nstars, stars, fp.want_candidates ? cands : nullptr);
+}
+
+extern "C" int sg_findstar_fit(sg_ctx *ctx, const sg_starfit_desc *desc, const uint16_t *frames, int nframes,
+		sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars, sg_starfit_cand *cands) {
+	if (!ctx || ctx->dev.empty())
+		return SG_ERR_GENERIC;
+	SgStarfitPlan fp;
+	int rc = sgs_check(ctx, desc, fp, frames, nframes, per_frame, nstars, stars, cands);
+	if (rc != SG_OK)
+		return rc;
+	const SgFindstarPlan &pl = fp.find;
+	SgDevice &dv = ctx->dev[0];
+	HIPCHK(hipSetDevice(dv.id));
+	const size_t total = (size_t)pl.W * pl.H * pl.C;
+	const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)1 << 29) / total));
+	HIPCHK(ensure(dv.fs_frames, (size_t)batch * total * sizeof(uint16_t)));
+	uint16_t *d = (uint16_t *)dv.fs_frames.p;
+	for (int f0 = 0; f0 < nframes; f0 += batch) {
+		const int nf = std::min(nframes - f0, batch);
+		HIPCHK(hipMemcpyAsync(d, frames + (size_t)f0 * total, (size_t)nf * total * sizeof(uint16_t), hipMemcpyHostToDevice,
+				dv.stream));
+		rc = sgf_run(ctx, 0, pl, d, nf, 0, per_frame + f0, nullptr, nullptr, nullptr, nullptr, &fp, nstars + f0,
+				stars ? stars + (size_t)f0 * fp.max_stars : nullptr,
+				fp.want_candidates && cands ? cands + (size_t)f0 * pl.max_candidates : nullptr);
+		if (rc != SG_OK)
+			return rc;
 	}
 	return SG_OK;
 }

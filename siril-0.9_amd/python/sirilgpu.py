@@ -100,6 +100,22 @@ class FindstarFrame(ctypes.Structure):
                 ("sigma_on_host", ctypes.c_int), ("threshold_wrapped", ctypes.c_int), ("no_data", ctypes.c_int)]
 
 
+class StarfitDesc(ctypes.Structure):
+    _fields_ = [("find", FindstarDesc), ("roundness", ctypes.c_double), ("norm", ctypes.c_double),
+                ("fwhm_scale_x", ctypes.c_double), ("fwhm_scale_y", ctypes.c_double),
+                ("max_stars", ctypes.c_int), ("want_candidates", ctypes.c_int)]
+
+
+# sg_star / sg_starfit_cand as numpy structured types; SG_FIT_* are the values of `status`
+FIT_FIELDS = ("B", "A", "x0", "y0", "sx", "sy", "fwhmx", "fwhmy", "mag", "rmse", "xpos", "ypos")
+STAR_DTYPE = np.dtype([("cand", "<i4"), ("x", "<i4"), ("y", "<i4"), ("iters", "<i4")] + [(k, "<f8") for k in FIT_FIELDS])
+CAND_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("iters", "<i4"), ("status", "<i4"), ("failed_test", "<i4"),
+                       ("reserved", "<i4"), ("init", "<f8", (6,))] + [(k, "<f8") for k in FIT_FIELDS])
+(SG_FIT_STAR, SG_FIT_NOT_ENOUGH_PIXELS, SG_FIT_NONFINITE, SG_FIT_BAD_FWHM, SG_FIT_NOT_STAR,
+ SG_FIT_OVER_CAP) = range(6)
+assert STAR_DTYPE.itemsize == 112 and CAND_DTYPE.itemsize == 168
+
+
 READ_REGION_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                   ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(Rect))
 CONT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p)
@@ -121,7 +137,8 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_seqfile_free", "sg_seqfile_get_info", "sg_seqfile_get_images", "sg_seqfile_set_image",
            "sg_seqfile_get_registration", "sg_seqfile_set_registration", "sg_seqfile_write",
            "sg_prepro_create", "sg_prepro_free", "sg_prepro_get_info", "sg_prepro_frames_device",
-           "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar"]
+           "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar",
+           "sg_findstar_fit_device", "sg_findstar_fit"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -243,6 +260,11 @@ def load():
     lib.sg_findstar_device.restype = ctypes.c_int
     lib.sg_findstar.argtypes = [P, ctypes.POINTER(FindstarDesc), P, ctypes.c_int, ctypes.POINTER(FindstarFrame), P, P, P]
     lib.sg_findstar.restype = ctypes.c_int
+    lib.sg_findstar_fit_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(StarfitDesc), P, ctypes.c_int, ctypes.c_int64,
+                                           ctypes.POINTER(FindstarFrame), P, P, P, P]
+    lib.sg_findstar_fit_device.restype = ctypes.c_int
+    lib.sg_findstar_fit.argtypes = [P, ctypes.POINTER(StarfitDesc), P, ctypes.c_int, ctypes.POINTER(FindstarFrame), P, P, P]
+    lib.sg_findstar_fit.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -469,6 +491,24 @@ def make_findstar_desc(W, H, C, layer, radius, sigma, area=None, max_candidates=
     if area is not None:
         d.area.x, d.area.y, d.area.w, d.area.h = [int(v) for v in area]
     return d
+
+
+def make_starfit_desc(W, H, C, layer, radius, sigma, area=None, max_candidates=2000, roundness=0.5, norm=65535.0,
+                      fwhm_scales=(1.0, 1.0), max_stars=2000, want_candidates=False):
+    d = StarfitDesc()
+    d.find = make_findstar_desc(W, H, C, layer, radius, sigma, area, max_candidates)
+    d.roundness, d.norm = roundness, norm
+    d.fwhm_scale_x, d.fwhm_scale_y = fwhm_scales
+    d.max_stars, d.want_candidates = max_stars, int(bool(want_candidates))
+    return d
+
+
+def _starfit_arrays(nframes, max_candidates, max_stars, want_candidates):
+    n = max(nframes, 0)
+    nstars = np.zeros(n, dtype=np.int32)
+    stars = np.zeros((n, max(max_stars, 0)), dtype=STAR_DTYPE)
+    cands = np.zeros((n, max(max_candidates, 0)), dtype=CAND_DTYPE) if want_candidates else None
+    return nstars, stars, cands
 
 
 def _findstar_arrays(nframes, radius, max_candidates, want_boxes):
@@ -731,6 +771,38 @@ class Context:
                                   bx.ctypes.data_as(ctypes.c_void_p) if want_boxes else None,
                                   wave.ctypes.data_as(ctypes.c_void_p) if want_wave else None)
         return rc, list(rec)[:N], xy, bx, wave
+
+    def findstar_fit_device(self, d_frames, nframes, C, H, W, radius, sigma, layer=0, area=None, max_candidates=2000,
+                            roundness=0.5, norm=65535.0, fwhm_scales=(1.0, 1.0), max_stars=2000,
+                            want_candidates=False, frame_stride=0, stream=None, dev_index=0):
+        """all of peaker on resident frames (sg_findstar_fit_device): candidates, PSF fit, is_star, sorted
+        star list.  Returns (rc, records, nstars[nframes] int32, stars[nframes][max_stars] of STAR_DTYPE,
+        cands[nframes][max_candidates] of CAND_DTYPE or None); frame f's stars are stars[f, :nstars[f]],
+        sorted by (mag, cand), its candidate records cands[f, :records[f].nstored]."""
+        d = make_starfit_desc(W, H, C, layer, radius, sigma, area, max_candidates, roundness, norm, fwhm_scales,
+                              max_stars, want_candidates)
+        rec = (FindstarFrame * max(nframes, 1))()
+        nstars, stars, cands = _starfit_arrays(nframes, max_candidates, max_stars, want_candidates)
+        rc = self.lib.sg_findstar_fit_device(self.ctx, dev_index, ctypes.byref(d), ctypes.c_void_p(d_frames), nframes,
+                                             frame_stride, rec, nstars.ctypes.data_as(ctypes.c_void_p),
+                                             stars.ctypes.data_as(ctypes.c_void_p),
+                                             cands.ctypes.data_as(ctypes.c_void_p) if want_candidates else None,
+                                             ctypes.c_void_p(stream) if stream else None)
+        return rc, list(rec)[:max(nframes, 0)], nstars, stars, cands
+
+    def findstar_fit(self, frames, radius, sigma, layer=0, area=None, max_candidates=2000, roundness=0.5,
+                     norm=65535.0, fwhm_scales=(1.0, 1.0), max_stars=2000, want_candidates=False):
+        """the same on host frames [N][C][H][W] u16 (sg_findstar_fit)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        N, C, H, W = frames.shape
+        d = make_starfit_desc(W, H, C, layer, radius, sigma, area, max_candidates, roundness, norm, fwhm_scales,
+                              max_stars, want_candidates)
+        rec = (FindstarFrame * max(N, 1))()
+        nstars, stars, cands = _starfit_arrays(N, max_candidates, max_stars, want_candidates)
+        rc = self.lib.sg_findstar_fit(self.ctx, ctypes.byref(d), frames.ctypes.data_as(ctypes.c_void_p), N, rec,
+                                      nstars.ctypes.data_as(ctypes.c_void_p), stars.ctypes.data_as(ctypes.c_void_p),
+                                      cands.ctypes.data_as(ctypes.c_void_p) if want_candidates else None)
+        return rc, list(rec)[:N], nstars, stars, cands
 
     def synth_fill(self, d_frames, nframes, C, H, W, row_begin, row_end, seed, maxshift, dev_index=0,
                    frame_stride=0, first_frame=0, plane_stride=0):
