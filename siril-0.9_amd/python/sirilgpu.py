@@ -632,6 +632,14 @@ class Context:
         self.check(rc, "sg_warp_u16")
         return out
 
+    def warp_device(self, d_in, W, H, C, d_out, oW, oH, hom, interpolation, stream=None, dev_index=0):
+        """the same on a resident image: d_in [C][H][W] -> d_out [C][oH][oW], device pointers
+        (sg_warp_u16_device).  With a stream the call returns once the kernel is queued on it."""
+        h = (ctypes.c_double * 9)(*[float(v) for v in np.asarray(hom, dtype=np.float64).reshape(9)])
+        rc = self.lib.sg_warp_u16_device(self.ctx, dev_index, ctypes.c_void_p(d_in), W, H, C, ctypes.c_void_p(d_out),
+                                         oW, oH, h, interpolation, ctypes.c_void_p(stream) if stream else None)
+        self.check(rc, "sg_warp_u16_device")
+
     def stack_seq(self, desc, seq):
         """Host-pull stack whose pull callback is the library's own sg_seq_read_region (C),
         i.e. stack_mean_with_rejection & co. reading the sequence's files directly."""

@@ -287,6 +287,26 @@ def star_case(i):
     return star_field(seed, H, W, n, margin=margin), r
 
 
+BATCH_SHAPE = (40, 48)          # [H][W] of the many-frame cases
+BATCH_FRAMES = (257, 258)       # one and two frames past the first chunk of sg_findstar_device
+BATCH_EMPTY_AREA = (7, 11, 6, 20)       # with r = 3: 2r >= the area's width, nothing to scan
+COPY_SWEEP_SHAPE = (31, 8500)   # no wavelet (H < 32), more pixels than k_findstar_copy's capped grid has threads
+
+
+def batch_sequence(nframes, tail):
+    """frames [nframes][1][40][48] for a call of more than one chunk: three star fields in rotation, then
+    `tail`, a list of plane numbers (3 = a fourth star field, -1 = an all-zero frame), as the last frames.
+    Returns (frames, plane number per frame, the four star fields)."""
+    H, W = BATCH_SHAPE
+    planes = [star_field(300 + i, H, W, 5, margin=8) for i in range(4)]
+    which = [i % 3 for i in range(nframes - len(tail))] + list(tail)
+    frames = np.zeros((nframes, 1, H, W), dtype=np.uint16)
+    for f, n in enumerate(which):
+        if n >= 0:
+            frames[f, 0] = planes[n]
+    return frames, which, planes
+
+
 def bright_frame(seed=3, S=1536):
     """S x S pixels bright enough that the sum of squares passes 2^53"""
     return np.random.default_rng(seed).integers(62000, 65535, size=(S, S)).astype(np.uint16)

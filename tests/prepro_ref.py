@@ -457,6 +457,23 @@ def fit_case(H, W, k_true, seed):
     return np.stack(frames)[:, None], dark
 
 
+BATCH_FRAMES = 257              # two chunks of sg_prepro_frames_device and one frame
+BATCH_SHAPE = (9, 67)
+BATCH_FRAMES_RGB = 129          # one chunk and one frame, three layers, no fit
+# (H, W, gap) of one-layer frames that k_prepro_calibrate's capped grid sweeps twice: through the 128-bit
+# body (stride a multiple of 8 samples, the frame not) and through the scalar loop
+SWEEP_VECTOR = (2050, 4101, 6)
+SWEEP_SCALAR = (1025, 1025, 3)
+
+
+def batch_fit_case():
+    """fit_case for a call of more than two chunks: (frames [257][1][9][67], dark [9][67], k_true), every
+    frame with a k_true of its own over [0.2, 1.7]"""
+    k_true = np.linspace(0.2, 1.7, BATCH_FRAMES)
+    frames, dark = fit_case(*BATCH_SHAPE, k_true, seed=sum(BATCH_SHAPE))
+    return frames, dark, k_true
+
+
 def edge_rows():
     """noise rows: (name, row, clip passes expected or None)"""
     rng = np.random.default_rng(5)

@@ -535,8 +535,8 @@ def peaker_tail(plane, cands, r, bg, roundness=0.5, norm=65535.0, scales=(1.0, 1
                 variants=("base",), tol=None):
     """peaker :200-247 on the stored candidates of one plane, serially.  Returns dict(records = one
     fit result per candidate (base variant, status FIT_OVER_CAP past the cap), stable [n] bool,
-    spread, stars = the indices of the accepted candidates sorted by (mag, cand)).  With one
-    variant every box counts as stable."""
+    spread, stars = the indices of the accepted candidates sorted by (mag, cand), fits = the records and
+    the stable mask before the cap, for cap_stars).  With one variant every box counts as stable."""
     tol = TOL if tol is None else tol
     bx = fsr.boxes(plane, cands, r)
     records, stable, spread = [], [], 0.0
@@ -550,6 +550,17 @@ def peaker_tail(plane, cands, r, bg, roundness=0.5, norm=65535.0, scales=(1.0, 1
         stable.append(st)
         if st:
             spread = max(spread, sp)
+    fits = (records, np.array(stable, dtype=bool))      # before the cap: what cap_stars takes
+    records, stable, stars = cap_stars(records, stable, max_stars, tol)
+    return dict(records=records, stable=stable, spread=spread, stars=stars, fits=fits)
+
+
+def cap_stars(records, stable, max_stars, tol=None):
+    """the end of peaker_tail on uncapped fit results (no status FIT_OVER_CAP among them): the cap, the
+    sorted star list and the mag pairs too close to order.  Returns (records, stable, stars); the arguments
+    are left as they are, so one set of fits serves every max_stars."""
+    tol = TOL if tol is None else tol
+    records = list(records)
     accepted = [n for n, o in enumerate(records) if o["status"] == FIT_STAR]
     for n in accepted[max_stars:]:
         records[n] = dict(records[n], status=FIT_OVER_CAP)
@@ -561,7 +572,7 @@ def peaker_tail(plane, cands, r, bg, roundness=0.5, norm=65535.0, scales=(1.0, 1
         ma, mb = float(records[a]["mag"]), float(records[b]["mag"])
         if abs(ma - mb) <= 100.0 * tol * max(abs(ma), abs(mb), 1.0):
             stable[a] = stable[b] = False
-    return dict(records=records, stable=stable, spread=spread, stars=stars)
+    return records, stable, stars
 
 
 # ---------------------------------------------------------------------------- GPU test cases
@@ -606,6 +617,38 @@ def starfit_frame(r):
     hx, hy = int(round(cx[2])) + 2, int(round(cy[2]))  # a hot pixel beside star 2
     img[hy, hx] = 60000
     return img
+
+
+DENSE_CASE = (78, 192, 192, 14, 14, 1.8, 3)     # seed, H, W, grid columns, grid rows, fwhm, radius
+
+
+def starfit_dense_frame():
+    """the construction of starfit_frame without its three special stars, dense enough that one frame
+    stores more than two 64-candidate steps of k_starfit_select (tests/test_batches_cpu.py holds the
+    counts): for r = 3, k = K_SIGMA"""
+    seed, H, W, gx, gy, fwhm, r = DENSE_CASE
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(F64)
+    img = rng.normal(800.0, 12.0, size=(H, W))
+    s = fwhm / 2.3548
+    cw, ch = (W - 2 * r - 1) / gx, (H - 2 * r - 1) / gy
+    cx = np.array([r + (i + 0.5) * cw for j in range(gy) for i in range(gx)]) + rng.uniform(-1.0, 1.0, size=gx * gy)
+    cy = np.array([r + (j + 0.5) * ch for j in range(gy) for i in range(gx)]) + rng.uniform(-1.0, 1.0, size=gx * gy)
+    amp = rng.uniform(6000, 40000, size=gx * gy)
+    for k in range(gx * gy):
+        img += amp[k] * np.exp(-((xx - cx[k]) ** 2 + (yy - cy[k]) ** 2) / (2 * s * s))
+    return np.clip(np.rint(img), 0, 65535).astype(np.uint16)
+
+
+def starfit_batch_sequence(nframes):
+    """frames [nframes][1][112][128] for a call of more than one chunk of 256: starfit_frame(5), its 180
+    degree rotation and an all-zero frame in rotation; frame 256 is the zero frame, frame 257 the
+    rotation.  Returns (frames, plane number per frame, the three planes)."""
+    a = starfit_frame(5)
+    planes = [a, np.ascontiguousarray(a[::-1, ::-1]), np.zeros_like(a)]
+    which = [i % 3 for i in range(nframes)]
+    which[256:] = [2, 1][:max(nframes - 256, 0)]
+    return np.stack([planes[w] for w in which])[:, None], which, planes
 
 
 def starfit_extra_frames():
