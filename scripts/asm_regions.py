@@ -2,8 +2,8 @@
 
   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -I../include -gline-tables-only \
         --cuda-device-only -S csrc/sg_stack_hist.hip -o hist.s
-  python3 scripts/asm_regions.py hist.s 'k_stack_histILi2ELi0ELi1E'                 # every basic block
-  python3 scripts/asm_regions.py hist.s 'k_stack_histILi2ELi0ELi1E' \
+  python3 scripts/asm_regions.py hist.s 'k_stack_histILi2ELi0EE'                 # every basic block
+  python3 scripts/asm_regions.py hist.s 'k_stack_histILi2ELi0EE' \
         --region pass=.LBB0_61-.LBB0_61+2 --region removal=.LBB0_70                  # sums over block runs
 
 The listing of the kernel whose symbol matches the pattern is cut into basic blocks at its labels

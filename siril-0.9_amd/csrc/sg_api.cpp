@@ -30,15 +30,14 @@ struct SgChainTables {
 
 template <int NREG, bool LISTED>
 __global__ void k_stack_sorted(SgStackParams p, const unsigned int *list, const unsigned int *list_count);
-template <int REJ, int NORM, int NI>
+template <int REJ, int NORM>
 __global__ void k_stack_hist(SgStackParams p, const int *tab, const int4 *norm, unsigned int *redo_count,
 		unsigned int *redo_list);
 __global__ void k_norm_fma_check(double *pairs, int N, int npad, int mode, unsigned int *verdict);
-template <int KM, int NW, bool PAIR>
+template <int KM, int NW>
 __global__ void k_stack_linfit(SgStackParams p, unsigned int *redo_count, unsigned int *redo_list);
-__global__ void k_hist_slow(SgStackParams p, unsigned int *redo_count, unsigned int *redo_list);
 void sg_dbg_why_dump(hipStream_t s);
-int sgh_block_threads(int ni, int rej);
+int sgh_block_threads(int rej);
 template <int NM>
 __global__ void k_stack_replay(SgStackParams p);
 __global__ void k_redo_to_literal(SgStackParams p, const unsigned int *list, const unsigned int *count,
@@ -129,8 +128,7 @@ extern "C" void sg_shutdown(sg_ctx *ctx) {
 			if (b->p)
 				(void)hipFree(b->p);
 		for (SgSlot &q : d.sl) {
-			SgBuf *sb[] = {&q.inb, &q.flag_list, &q.flag_map, &q.redo, &q.cmp_cols, &q.cmp_list, &q.scratch, &q.lin_tab,
-				&q.wx};
+			SgBuf *sb[] = {&q.inb, &q.flag_list, &q.flag_map, &q.redo, &q.cmp_cols, &q.cmp_list, &q.scratch, &q.lin_tab};
 			for (SgBuf *b : sb)
 				if (b->p)
 					(void)hipFree(b->p);
@@ -228,16 +226,12 @@ typedef void (*SgReduce3Fn)(SgStackParams, const int *, const int *);
 typedef void (*SgLinfitFn)(SgStackParams, unsigned int *, unsigned int *);
 typedef void (*SgReplayFn)(SgStackParams);
 
-/* k_stack_hist<REJ, NORM, NI>: rows REJ = 1 PERCENTILE, 2 SIGMA, 3 SIGMEDIAN, 4 WINSORIZED, 8 stack_median */
+/* k_stack_hist<REJ, NORM>: rows REJ = 1 PERCENTILE, 2 SIGMA, 3 SIGMEDIAN, 4 WINSORIZED, 8 stack_median */
 static constexpr int SG_HIST_REJ[5] = {1, 2, 3, 4, 8};
-#define SG_HIST_ROW(R) {{k_stack_hist<R, 0, 1>, nullptr}, {k_stack_hist<R, 1, 1>, nullptr}, \
-		{k_stack_hist<R, 2, 1>, nullptr}, {k_stack_hist<R, 3, 1>, nullptr}}
-#define SG_HIST_ROW2(R) {{k_stack_hist<R, 0, 1>, k_stack_hist<R, 0, 2>}, {k_stack_hist<R, 1, 1>, nullptr}, \
-		{k_stack_hist<R, 2, 1>, nullptr}, {k_stack_hist<R, 3, 1>, nullptr}}
-static constexpr SgHistFn SG_HIST_KERNELS[5][4][2] = {	/* [REJ row][NORM][NI - 1] */
-	SG_HIST_ROW(1), SG_HIST_ROW2(2), SG_HIST_ROW(3), SG_HIST_ROW2(4), SG_HIST_ROW(8)};
+#define SG_HIST_ROW(R) {k_stack_hist<R, 0>, k_stack_hist<R, 1>, k_stack_hist<R, 2>, k_stack_hist<R, 3>}
+static constexpr SgHistFn SG_HIST_KERNELS[5][4] = {	/* [REJ row][NORM] */
+	SG_HIST_ROW(1), SG_HIST_ROW(2), SG_HIST_ROW(3), SG_HIST_ROW(4), SG_HIST_ROW(8)};
 #undef SG_HIST_ROW
-#undef SG_HIST_ROW2
 
 #define SG_SORTED_ROW(R) {k_stack_sorted<R, false>, k_stack_sorted<R, true>}
 static constexpr SgSortedFn SG_SORTED_KERNELS[5][2] = {	/* [log2 NREG][LISTED] */
@@ -249,11 +243,9 @@ static constexpr SgReduce3Fn SG_REDUCE3_KERNELS[5][3] = {	/* [M][log2 SEG] */
 	SG_R3_ROW(0), SG_R3_ROW(1), SG_R3_ROW(2), SG_R3_ROW(3), SG_R3_ROW(4)};
 #undef SG_R3_ROW
 
-static constexpr SgLinfitFn SG_LINFIT_KERNELS[2][3][2] = {	/* [KM / 16][log2 (NW / 4)][PAIR] */
-	{{k_stack_linfit<8, 4, false>, k_stack_linfit<8, 4, true>}, {k_stack_linfit<8, 8, false>, k_stack_linfit<8, 8, true>},
-		{k_stack_linfit<8, 16, false>, nullptr}},
-	{{k_stack_linfit<16, 4, false>, k_stack_linfit<16, 4, true>}, {k_stack_linfit<16, 8, false>, k_stack_linfit<16, 8, true>},
-		{nullptr, nullptr}}};
+static constexpr SgLinfitFn SG_LINFIT_KERNELS[2][3] = {	/* [KM / 16][log2 (NW / 4)] */
+	{k_stack_linfit<8, 4>, k_stack_linfit<8, 8>, k_stack_linfit<8, 16>},
+	{k_stack_linfit<16, 4>, k_stack_linfit<16, 8>, nullptr}};
 
 static constexpr SgReplayFn SG_REPLAY_KERNELS[2] = {k_stack_replay<512>, k_stack_replay<SG_REPLAY_MAXN>};	/* [N > 512] */
 
@@ -266,14 +258,14 @@ static int log2_index(int v, int n) {	/* i with v == 1 << i below n, else -1 */
 
 static const void *hist_kernel(const SgStackPlan &pl) {
 	for (int r = 0; r < 5; r++)
-		if (SG_HIST_REJ[r] == pl.rj && pl.norm >= 0 && pl.norm < 4 && pl.ni >= 1 && pl.ni <= 2)
-			return (const void *)SG_HIST_KERNELS[r][pl.norm][pl.ni - 1];
+		if (SG_HIST_REJ[r] == pl.rj && pl.norm >= 0 && pl.norm < 4)
+			return (const void *)SG_HIST_KERNELS[r][pl.norm];
 	return nullptr;
 }
 
 static const void *linfit_kernel(const SgStackPlan &pl) {
 	const int w = log2_index(pl.nw / 4, 3);
-	return (pl.km == 8 || pl.km == 16) && w >= 0 ? (const void *)SG_LINFIT_KERNELS[pl.km / 16][w][pl.pair ? 1 : 0] : nullptr;
+	return (pl.km == 8 || pl.km == 16) && w >= 0 ? (const void *)SG_LINFIT_KERNELS[pl.km / 16][w] : nullptr;
 }
 
 static hipError_t launch_sorted(int nreg, bool listed, dim3 grid, size_t lds, hipStream_t s, const SgStackParams &p,
@@ -303,7 +295,6 @@ enum SgFlagWord {
 	SG_FL_REDO = 2,		/* redo count of the histogram / linfit kernels */
 	SG_FL_COMPACT = 3,	/* compact columns taken */
 	SG_FL_LOOP_FAULT = 4,	/* a SIGMEDIAN pixel's reference loop never ends */
-	SG_FL_EXPORT = 6,	/* exported WINSORIZED columns */
 	SG_FL_VERDICT = 7,	/* k_norm_fma_check's load verdict */
 	SG_FL_SUM_MAX = 16	/* SUM maximum, words 16 and 17 as one little-endian 64-bit value (byte 64: kept across
 				 * the bands of a streamed SUM); the uint32_t kernels write word 16 alone, 17 stays 0 */
@@ -332,7 +323,6 @@ static int stack_fold(sg_ctx *ctx, SgDevice &dv, int slot, uint64_t rej[3][2], u
 	if (st.path == 1)
 		st.chain_pixels = fl[SG_FL_REDO];
 	st.compact_pixels = std::min<uint64_t>(fl[SG_FL_COMPACT], st.compact_pixels);	/* pstats holds the capacity */
-	st.exported_pixels = st.exported_pixels ? std::min<uint64_t>(fl[SG_FL_EXPORT], st.exported_pixels) : 0;	/* capacity, as compact */
 	if (st.norm_fma > 0)	/* k_norm_fma_check's verdict, read back beside the counters (the launch set the best allowed) */
 		st.norm_fma = st.norm_fma == 2 && !(fl[SG_FL_VERDICT] & 2u) ? 2 : (fl[SG_FL_VERDICT] & 1u) ? 0 : 1;
 	if (sync) {	/* the calling stack_device_core publishes dv.stats when it returns */
@@ -467,13 +457,6 @@ static int prepare_rejection_buffers(StackCall &c, const SgStackPlan &pl) {
 		p.cmp_count = c.fl + SG_FL_COMPACT;	/* cleared with the counters */
 		p.cmp_cap = (unsigned int)pl.cmp_cap;
 	}
-	if (pl.wexp) {
-		HIPCHK(ensure(sb.wx, pl.wx_cap * (SG_HIST_HROWS + 3) * sizeof(uint32_t)));
-		p.wx = (uint32_t *)sb.wx.p;
-		p.wx_cap = (unsigned int)pl.wx_cap;
-		p.wx_count = c.fl + SG_FL_EXPORT;	/* cleared with the counters */
-		p.wx_kmax = pl.wx_kmax;
-	}
 	return SG_OK;
 }
 
@@ -565,8 +548,8 @@ static int to_tail(StackCall &c, const SgStackPlan &pl, bool async) {
 /* A/B (probe builds): report the resident histogram workgroups per CU */
 static void report_hist_occupancy(const StackCall &c, const SgStackPlan &pl) {
 	int per_cu = -1;
-	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)SG_HIST_KERNELS[1][0][pl.ni == 2 ? 1 : 0],
-			sgh_block_threads(pl.ni, 2), (size_t)pl.hist_ldspad);
+	(void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)SG_HIST_KERNELS[1][0],
+			sgh_block_threads(2), (size_t)pl.hist_ldspad);
 	hipDeviceProp_t prop;
 	(void)hipGetDeviceProperties(&prop, c.dv->id);
 	fprintf(stderr, "k_stack_hist: %d workgroups/CU (lds/CU %zu, lds/block max %zu, pad %d)\n", per_cu,
@@ -598,11 +581,7 @@ static int launch_rejection_main(StackCall &c, const SgStackPlan &pl) {
 			return set_err(ctx, SG_ERR_GENERIC, "no histogram kernel for this case%s%.0ld", "", 0);
 		const int4 *norm_pairs = (const int4 *)p.hist_norm;
 		void *args[] = {&p, &p.hist_tab, &norm_pairs, &redo_count, &c.redo_list};
-		HIPCHK(hipLaunchKernel(kf, grid, dim3((unsigned)sgh_block_threads(pl.ni, pl.rj)), args, pl.main_lds, c.s));
-		if (pl.wexp) {	/* the exported columns, before anything reads the redo list */
-			hipLaunchKernelGGL(k_hist_slow, dim3(3072), dim3(64), 0, c.s, p, redo_count, c.redo_list);	/* 12 waves per CU (153 VGPRs) */
-			HIPCHK(hipGetLastError());
-		}
+		HIPCHK(hipLaunchKernel(kf, grid, dim3((unsigned)sgh_block_threads(pl.rj)), args, pl.main_lds, c.s));
 	} else if (pl.main == SG_MAIN_LINFIT) {
 		const void *kf = linfit_kernel(pl);
 		if (!kf)
@@ -738,7 +717,6 @@ static int launch_stack(StackCall &c, const SgStackPlan &pl, int sum_mode, bool 
 	st.launches = pl.launches;
 	st.main_kernel_blocks = pl.main_kernel_blocks;
 	st.compact_pixels = pl.compact ? pl.cmp_cap : 0;
-	st.exported_pixels = pl.wexp ? pl.wx_cap : 0;
 	st.norm_fma = pl.norm_fma;
 	if (!pl.rejection_family) {
 		if (int rc = stage_inputs(c, pl))
@@ -1221,7 +1199,6 @@ static void publish_multi_stats(sg_ctx *ctx, int G) {
 		agg.slow_pixels += s.slow_pixels;
 		agg.chain_pixels += s.chain_pixels;
 		agg.compact_pixels += s.compact_pixels;
-		agg.exported_pixels += s.exported_pixels;
 		agg.norm_fma = std::max(agg.norm_fma, s.norm_fma);
 		agg.launches += s.launches;
 		agg.main_kernel_blocks += s.main_kernel_blocks;

@@ -9,7 +9,7 @@
 #define SG_STAGE_STRIDE 66	/* u16 per staged frame row: 64 px + 2 pad -> 33 dwords, bank-conflict free */
 #define SG_SORT_THREADS 256
 #define SG_REJ_SHARDS 1024
-/* A/B probe modes of the stacking kernels (SG_HIST_DBG: phase timings, loads only, timelines,
+/* A/B probe modes of the stacking kernels (SG_HIST_DBG: phase timings, loads only,
  * occupancy reports): compiled in only by a probe build (make EXTRA=-DSG_DBG_MODES=1 BUILD=...);
  * the product kernels carry no branch on them */
 #ifndef SG_DBG_MODES
@@ -24,10 +24,6 @@ enum { SG_CLS_OK = 0, SG_CLS_LITERAL = 1, SG_CLS_CHAIN = 2, SG_CLS_DONE = 3,
 #define SG_REPLAY_WAVES 2
 #define SG_REPLAY_MAXN 2048
 #define SG_REDO_REPLAY_MAX 32768	/* histogram redo pixels sent straight to k_stack_replay (measured: 22 k faster there, 113 k slower) */
-
-/* dwords per pixel column of the histogram kernels' LDS histogram: 64 band dwords (256 u8 bins)
- * and the out-of-band count (sg_stack_hist.hip SGH_HROWS) */
-#define SG_HIST_HROWS 65
 
 /* everything the stacking kernels need, passed by value */
 struct SgStackParams {
@@ -83,16 +79,6 @@ struct SgStackParams {
 	const unsigned int *rp_list, *rp_count;
 	unsigned int rp_maxn;
 	const double *linfit_tab;		/* LINEARFIT: gsl_fit_linear's m_x, m_dx2 per N (k_linfit_tables) */
-	/* histogram WINSORIZED without normalisation (SG_WINS_EXPORT): the tile exports the columns that
-	 * hold a zero or a 65535 sample (the slow Winsorize pixels) instead of finishing them, and
-	 * k_hist_slow finishes them in waves of their own: wx[j * wx_cap + slot], rows j < SGH_HROWS the
-	 * column's histogram dwords, then lo, nz | ns << 16, the pixel index; wx_count (device) the slots
-	 * taken (null wx: every column finished in its tile) */
-	uint32_t *wx;				/* [SG_HIST_HROWS + 3][wx_cap] */
-	unsigned int wx_cap;
-	unsigned int *wx_count;
-	int wx_kmax;				/* export a column with 1 .. wx_kmax zero / 65535 samples (more: the rows a
-						 * registration shift empties, whose tiles are slow throughout: finished there) */
 	uint32_t *sum_buf;			/* SUM: raw sums [C][H][W] (unsigned long long in the wide kernels, sg_reduce_one) */
 	unsigned int *maxim;			/* SUM: global max of sums (8-byte aligned; unsigned long long in the wide kernels) */
 };

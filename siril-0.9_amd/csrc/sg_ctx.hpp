@@ -36,7 +36,7 @@ struct SgReader {
  * once the call two back has been folded).  Synchronous calls use slot 0. */
 struct SgSlot {
 	SgBuf inb;		/* the call's inputs (shift table, normalisation pairs, chain tables) */
-	SgBuf flag_list, flag_map, redo, cmp_cols, cmp_list, scratch, lin_tab, wx;
+	SgBuf flag_list, flag_map, redo, cmp_cols, cmp_list, scratch, lin_tab;
 	/* pinned, host-mapped staging of the inputs (k_stage_copy reads it); stage_ev marks the copy
 	 * done before the host block is rewritten */
 	void *stage_h = nullptr, *stage_d = nullptr;
@@ -125,7 +125,6 @@ struct SgKnobs {
 	int hist_dbg = 0;		/* SG_HIST_DBG: k_stack_hist phase / timing A/B (0 = production) */
 	int hist_prio = 1;		/* SG_HIST_PRIO: build-phase wave priority (1 measured best, scripts/gpu_prio.sh) */
 	int hist_ldspad = 0;		/* SG_HIST_LDSPAD: extra LDS bytes per histogram workgroup (occupancy A/B) */
-	int hist_ni = 1;		/* SG_HIST_NI: pixel pairs per lane of the histogram tiles (2: 256-px tiles) */
 	int wins_cap = 64;		/* SG_WINS_CAP: histogram Winsorize inner iterations per pass before the redo list */
 	int redo_replay = 1;		/* SG_REDO_REPLAY: 0 = redo list always through the sorted kernel */
 	int hist_compact = 1;		/* SG_HIST_COMPACT: 0 = normalised redo pixels gather their columns again,
@@ -151,8 +150,6 @@ struct SgKnobs {
 	int reg_qafter = 0;		/* SG_REG_QAFTER: 1 = the quality estimate queued after the first batch's forward rows (beside the column pass) */
 	int reg_qfold = 12;		/* SG_REG_QFOLD = r (3, 6, 9 ...): QualityEstimate's 3x3 subsample folded into the wave-level forward row pass, r consecutive rows per wave (S = 2048, fp32; configs[1] registration 3.10 -> 2.95 ms, r = 6-12 equal, 24 / 48 slower, profiles/r06s_*, r06t_*); 0 = k_quality_sub */
 	int linfit_waves = 8;		/* SG_LINFIT_WAVES: waves per 64-pixel k_stack_linfit tile (4, 8 or 16 (KM = 8)) */
-	int wins_export = 0;		/* SG_WINS_EXPORT = k > 0: histogram WINSORIZED (no normalisation) exports its columns holding 1 .. k zero / 65535 samples to k_hist_slow */
-	int linfit_pair = 0;		/* SG_LINFIT_PAIR: 1 = both pixels of a sorted pair through one lockstep pass loop (lfx_pixel2_m) */
 	int linfit_fast = 1;		/* SG_LINFIT_FAST: 1 = LINEARFIT through the decision-exact k_stack_linfit (16 <= N <= 1024), redo pixels to the sorted kernel; 0 = every pixel through the sorted kernel */
 	int qgrad_stream = 1;		/* SG_QGRAD_STREAM: 1 = the quality gradient streamed down 60-column bands (k_quality_grad_s), 0 = tiled */
 	int reg_wcolw = 8;		/* SG_REG_WCOLW: columns per strip of the wave-level column pass (8: 64-B row segments, one workgroup per CU: configs[1] registration 3.33 -> 3.20 ms and the pass's HBM writes 1.57x -> 1.0x the plane, profiles/r05w_*; 4: 32-B segments, two workgroups per CU) */
@@ -166,7 +163,6 @@ struct SgKnobs {
 		hist_dbg = sg_env_int("SG_HIST_DBG", 0, 1000, 0);
 		hist_prio = sg_env_int("SG_HIST_PRIO", 0, 3, 1);
 		hist_ldspad = sg_env_int("SG_HIST_LDSPAD", 0, 160 * 1024, 0);
-		hist_ni = sg_env_int("SG_HIST_NI", 1, 2, 1);
 		wins_cap = sg_env_int("SG_WINS_CAP", 4, 100000, 64);
 		redo_replay = sg_env_int("SG_REDO_REPLAY", 0, 1, 1);
 		hist_compact = sg_env_int("SG_HIST_COMPACT", 0, 1 << 30, 1);
@@ -203,8 +199,6 @@ struct SgKnobs {
 		qgrad_stream = sg_env_int("SG_QGRAD_STREAM", 0, 1, 1);
 		linfit_fast = sg_env_int("SG_LINFIT_FAST", 0, 1, 1);
 		linfit_waves = sg_env_int("SG_LINFIT_WAVES", 4, 16, 8);
-		linfit_pair = sg_env_int("SG_LINFIT_PAIR", 0, 1, 0);
-		wins_export = sg_env_int("SG_WINS_EXPORT", 0, 65535, 0);
 		reg_qafter = sg_env_int("SG_REG_QAFTER", 0, 1, 0);
 		reg_rpw = sg_env_int("SG_REG_RPW", 1, 64, 8);
 		reg_qfold = sg_env_int("SG_REG_QFOLD", 0, 63, 12) / 3 * 3;

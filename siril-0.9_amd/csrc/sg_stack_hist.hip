@@ -39,38 +39,24 @@
 
 #define SGH_BINS 256
 #define SGH_DW (SGH_BINS / 4)	/* band dwords per pixel */
-/* A tile is NI * 128 pixels of one row, streamed by NI * 4 waves: every lane loads NI dwords
- * (pixel pairs) per frame, instruction i covering the tile's 256-byte segment i.  Pixel pair i
- * of lane l = pixels 128 i + 2 l (column 64 (2 i) + l) and 128 i + 2 l + 1 (column
- * 64 (2 i + 1) + l).  NI = 2 reads each frame row as one contiguous 512-byte segment (a
- * shifted row straddles 5 128-B lines per 512 B instead of 3 per 256 B: tools/bw_probe4.hip
- * streams the 512 x 4096^2 sequence in 2.94 ms against 3.20 ms), but two 8-wave workgroups per
- * CU overlap one tile's finish with the other's loads worse than four 4-wave ones: 4.62 ms
- * against 4.22 ms for the whole kernel, so NI = 1 is the default (SG_HIST_NI=2 selects 2). */
-#define SGH_WAVES_PER_NI 4
-/* waves per 256-pixel tile (NI = 2, the A/B SG_HIST_NI=2): 8, or 4 (-DSGH_WAVES_NI2=4: each
- * lane loads both dwords of a 512-byte row segment, two 4-wave workgroups per CU with up to
- * 256 VGPRs).  Measured (scripts/gpu_r4h.sh, profiles/r02x_ab_ni2_waves.log): 4 waves 5.02-5.08
- * ms (loads only 3.36), 8 waves 4.37 ms, the 128-pixel default 3.50 ms (loads only 3.23) */
-#ifndef SGH_WAVES_NI2
-#define SGH_WAVES_NI2 8
-#endif
-#ifndef SGH_NB2
-#define SGH_NB2 1	/* blocks in flight for NI = 2 (4 waves: NB2 = 2 5.08 ms, 1 5.02 ms) */
-#endif
-template <int NI>
-struct SghCfg {
-	static constexpr int WAVES = NI == 1 ? SGH_WAVES_PER_NI : SGH_WAVES_NI2;
-	static constexpr int WPE = NI == 1 ? 4 : (SGH_WAVES_NI2 == 4 ? 2 : 4);	/* waves per SIMD (launch bound) */
-};
+/* A tile is 128 pixels of one row, streamed by 4 waves: every lane loads one dword (a pixel
+ * pair) per frame, a wave covering the tile's 256-byte row segment.  The pair of lane l =
+ * pixels 2 l (column l) and 2 l + 1 (column 64 + l).  256-pixel tiles (two dwords per lane,
+ * 8 or 4 waves) lost on every measurement (4.62 against 4.22 ms and 4.37 against 3.50 ms,
+ * profiles/r02x_ab_ni2_waves.log) and were removed. */
+/* Pixel pairs per lane: 1.  The build keeps its register buffers and counters as [SGH_NP]
+ * arrays with a loop over the pair index: written as scalars the same arithmetic compiles to
+ * another instruction schedule in all twenty kernels (fewer SGPR spill moves, other load
+ * grouping), none of it measured; this form keeps the generated code that the recorded
+ * timings belong to ("Retired A/B variants") */
+constexpr int SGH_NP = 1;
+#define SGH_WAVES 4	/* waves per tile */
+#define SGH_WPE 4	/* waves per SIMD (launch bound) */
 #ifndef SGH_WINS_WAVES
 #define SGH_WINS_WAVES 2	/* waves per 128-pixel WINSORIZED tile: 2, each building twice the frames, so 4 tiles fit a CU at 2 waves per SIMD (26.5 -> 25.7 ms on configs[4], profiles/r03_wins_ab.log); 4: the SIGMA shape */
 #endif
-/* waves of a tile of kernel k_stack_hist<REJ, ., NI> */
-template <int REJ, int NI>
-struct SghW {
-	static constexpr int WAVES = (REJ == 4 && NI == 1) ? SGH_WINS_WAVES : SghCfg<NI>::WAVES;
-};
+/* waves of a tile of kernel k_stack_hist<REJ, .> */
+#define SGH_TILE_WAVES(REJ) ((REJ) == 4 ? SGH_WINS_WAVES : SGH_WAVES)
 #ifndef SGH_CENTER
 #define SGH_CENTER 16		/* frames used for the centre estimate */
 #endif
@@ -91,22 +77,20 @@ typedef unsigned short sgh_u16x2 __attribute__((ext_vector_type(2)));
  *   h[half][64][l]               : samples outside the band (u32: zeros, 65535s; anything
  *                                  else sends the pixel to the redo list) */
 #define SGH_HROWS (SGH_DW + 1)
-static_assert(SGH_HROWS == SG_HIST_HROWS, "sg_common.hpp's column size");
 #define SGH_OVK 4	/* out-of-band sample values captured per column (normalised stacks) */
-template <int NI>
 struct alignas(16) SghLds {
-	uint32_t h[2 * NI][SGH_HROWS][64];
-	uint32_t nz[128 * NI], ns[128 * NI];	/* zeros / 65535s (all of them lie outside the band) */
-	uint32_t na[128 * NI];			/* samples above the band (stack_median / PERCENTILE kernels only) */
-	uint32_t lo2[NI][64];			/* band starts of the lane pixel pairs (u16 halves) */
-	uint32_t cs[NI][8][64];			/* wave 1's first 8 frames for the band centre (SGH_CENTER2W) */
+	uint32_t h[2][SGH_HROWS][64];
+	uint32_t nz[128], ns[128];		/* zeros / 65535s (all of them lie outside the band) */
+	uint32_t na[128];			/* samples above the band (stack_median / PERCENTILE kernels only) */
+	uint32_t lo2[SGH_NP][64];		/* band starts of the lane pixel pairs (u16 halves) */
+	uint32_t cs[SGH_NP][8][64];		/* wave 1's first 8 frames for the band centre (SGH_CENTER2W) */
 	uint8_t perm[128];			/* WINSORIZED finish order of the columns (SGH_WINS_ORDER) */
 	/* normalised SIGMA / WINSORIZED builds: the first SGH_OVK out-of-band samples of a column
 	 * that are neither 0 nor 65535, and how many there were (sgh_capture, sgh_compact) */
-	uint16_t ov[SGH_OVK][128 * NI];
-	uint32_t ovn[128 * NI];
+	uint16_t ov[SGH_OVK][128];
+	uint32_t ovn[128];
 #ifdef SGH_WPROF
-	uint64_t wp[SghCfg<NI>::WAVES][16];	/* probe build: per-wave region cycles and events (sgh_wp) */
+	uint64_t wp[SGH_WAVES][16];	/* probe build: per-wave region cycles and events (sgh_wp) */
 #endif
 };
 
@@ -495,13 +479,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t sgh_rsrc(const char *base, uin
  * straddling the left edge loads one pixel to the right and the binning moves the valid
  * pixel to the high half (<< 16), one straddling the right edge loads one pixel to the
  * left (>> 16); two fix bits per frame in `fix` */
-template <bool FULL, bool EDGE, int NI, int MB = 16, int MO = 0>
+template <bool FULL, bool EDGE, int MB = 16, int MO = 0>
 __device__ __forceinline__ void sgh_loadblk(const SghFrame &F, const SghTab16 &T, int N, int f0,
-		uint32_t (&dst)[MB][NI], uint32_t (&fix)[NI]) {
+		uint32_t (&dst)[MB][SGH_NP], uint32_t (&fix)[SGH_NP]) {
 	const char *b = F.plane0 + (int64_t)f0 * F.fstride2;
 	if (EDGE) {
 #pragma unroll
-		for (int i = 0; i < NI; i++)
+		for (int i = 0; i < SGH_NP; i++)
 			fix[i] = 0;
 	}
 #pragma unroll
@@ -509,8 +493,8 @@ __device__ __forceinline__ void sgh_loadblk(const SghFrame &F, const SghTab16 &T
 		const uint32_t nrec = (FULL || f0 + m < N) ? F.plane_bytes : 0u;
 		const uint32_t k = (uint32_t)(F.rw2 - T.c1[MO + m]);
 #pragma unroll
-		for (int i = 0; i < NI; i++) {
-			const uint32_t xa2 = F.xa2 + 256u * i;	/* the lane's pair in segment i */
+		for (int i = 0; i < SGH_NP; i++) {
+			const uint32_t xa2 = F.xa2 + 256u * i;	/* the lane's pair */
 			uint32_t off = k + xa2;
 			if (EDGE) {
 				const int mt = MO + m;
@@ -521,7 +505,7 @@ __device__ __forceinline__ void sgh_loadblk(const SghFrame &F, const SghTab16 &T
 				fix[i] |= ((bada && !badb) ? 1u : ((!bada && badb) ? 2u : ((bada && badb) ? 3u : 0u))) << (2 * m);
 			}
 			/* interior tiles: the frame's term (R - sy) W 2 + 2 (x0 - sx), the shifted start of
-			 * the tile's row segment, goes in the SGPR offset and the lane's voffset 4 l + 256 i
+			 * the tile's row segment, goes in the SGPR offset and the lane's voffset 4 l
 			 * stays fixed (no VALU per load).  The segment start is >= 0 for a row inside the
 			 * frame (x0 >= max |sx| in an interior tile) and < 0 for a row above it; gfx950
 			 * bounds-checks the unsigned sum voffset + soffset without wrapping
@@ -729,8 +713,7 @@ __device__ __forceinline__ void sgh_bin_pair2(uint32_t *h, uint32_t l4, uint32_t
  * scattered line per sample (1.2 % of the pixels under multiplicative scaling, 1.65 ms of
  * staging for 0.2 GB of data); with the few values known the finish writes the pixel's
  * sorted column itself (sgh_compact).  A rare branch: the test is four VALU ops per pair */
-template <int NI>
-__device__ __forceinline__ void sgh_capture(SghLds<NI> &L, int i, int lane, uint32_t lo2, uint32_t v, uint32_t k1,
+__device__ __forceinline__ void sgh_capture(SghLds &L, int i, int lane, uint32_t lo2, uint32_t v, uint32_t k1,
 		uint32_t ksat, uint32_t k255) {
 	/* packed: sat(v - lo - 255) > 0 (outside the band) and min(v, 1) - sat(v - 65534) = 1 (not 0,
 	 * not 65535); the last two are the build's own counter terms (shared after inlining) */
@@ -1686,8 +1669,7 @@ __device__ __forceinline__ int sgh_median_pct(const SghPix &P, int N, double sl,
  * expanded bin by bin, those above it, 65535s) and its pixel to p.cmp_list[slot];
  * k_stack_sorted<., true> then stages the column with coalesced loads instead of N scattered
  * ones.  A pixel past p.cmp_cap goes to the redo list as before.  Wave-uniform control flow */
-template <int NI>
-__device__ __forceinline__ void sgh_compact(const SgStackParams &p, const SghLds<NI> &L, bool want, int col, int lo,
+__device__ __forceinline__ void sgh_compact(const SgStackParams &p, const SghLds &L, bool want, int col, int lo,
 		unsigned int pix, int nzl, int nsl, int kl, unsigned int *__restrict__ redo_count,
 		unsigned int *__restrict__ redo_list) {
 	const int lane = threadIdx.x & 63;
@@ -1762,8 +1744,8 @@ __device__ __forceinline__ void sgh_compact(const SgStackParams &p, const SghLds
 /* pixel column `col` of the tile (x its image column); PAIR: lane pair half `half`, else one
  * lane per column (half = 0); CAP: normalised SIGMA / WINSORIZED kernel (captured out-of-band
  * values, sgh_compact) */
-template <int REJ, bool PAIR, int NI, bool ZT = false, bool CAP = false, class LT = SghLds<NI>>
-__device__ __forceinline__ void sgh_finish2(const SgStackParams &p, LT &L, int col, int half, int lo, int R, int c, int x,
+template <int REJ, bool PAIR, bool ZT = false, bool CAP = false>
+__device__ __forceinline__ void sgh_finish2(const SgStackParams &p, SghLds &L, int col, int half, int lo, int R, int c, int x,
 		unsigned int *__restrict__ redo_count, unsigned int *__restrict__ redo_list, bool zrow = false) {
 	const int lane = threadIdx.x & 63;
 	const int N = p.N;
@@ -1773,8 +1755,6 @@ __device__ __forceinline__ void sgh_finish2(const SgStackParams &p, LT &L, int c
 			p.out[((int64_t)c * p.H + R) * p.W + x] = (uint16_t)(hc[0] + L.nz[col]);
 		return;
 	}
-	/* A/B timeline (dbg 11): cycles of the prefix and of the pass loop, passes per wave */
-	const uint64_t c0 = SG_DBG(p) == 11 ? __builtin_readcyclecounter() : 0;
 #ifdef SGH_WPROF
 	if (REJ == 4 && lane == 0) {
 		uint64_t *w = L.wp[threadIdx.x >> 6];
@@ -1880,7 +1860,6 @@ __device__ __forceinline__ void sgh_finish2(const SgStackParams &p, LT &L, int c
 	uint16_t value = 0;
 	uint32_t rlo = 0, rhi = 0;
 	bool cmp = false;	/* CAP: the pixel's sorted column goes out through sgh_compact */
-	const uint64_t c1 = SG_DBG(p) == 11 ? __builtin_readcyclecounter() : 0;
 	if (x < p.W) {
 		/* CAP SIGMA (round 6): up to SGH_OVK out-of-band samples other than 0 / 65535, every one captured
 		 * (their values in L.ov: a scaled cosmic ray, a dead pixel moved off 0), join the pixel as known
@@ -1981,8 +1960,7 @@ __device__ __forceinline__ void sgh_finish2(const SgStackParams &p, LT &L, int c
 		if (!half) {
 			if (cls == SG_CLS_OK) {
 #ifndef SGH_WPROF
-				if (SG_DBG(p) != 11)	/* the timeline A/B keeps its stamps in the output buffer */
-					p.out[pix] = value;
+				p.out[pix] = value;
 #endif
 			} else if (!cmp) {
 #ifndef SGH_WPROF
@@ -1993,20 +1971,6 @@ __device__ __forceinline__ void sgh_finish2(const SgStackParams &p, LT &L, int c
 		}
 		if (cls != SG_CLS_OK || half)
 			rlo = rhi = 0;
-	}
-	if (SG_DBG(p) == 11 && NI == 2) {
-		const uint64_t c2 = __builtin_readcyclecounter();
-		int pmax = passes, psum = passes;
-		for (int o = 32; o > 0; o >>= 1) {
-			pmax = max(pmax, __shfl_xor(pmax, o, 64));
-			psum += __shfl_xor(psum, o, 64);
-		}
-		if (lane == 0) {
-			uint64_t *tw = (uint64_t *)p.out + (size_t)blockIdx.x * 32 + 4 + 3 * (threadIdx.x >> 6);
-			tw[0] = c1 - c0;
-			tw[1] = c2 - c1;
-			tw[2] = (uint64_t)pmax | ((uint64_t)psum << 16);
-		}
 	}
 	/* wave sums of the rejection counts (each lane's count <= N, so a wave's sum of 32 pixel
 	 * counts fits 32 bits for any N the kernel takes): DPP row sums + 4 readlanes instead of
@@ -2024,7 +1988,7 @@ __device__ __forceinline__ void sgh_finish2(const SgStackParams &p, LT &L, int c
 	}
 #endif
 	if constexpr (CAP)
-		sgh_compact<NI>(p, L, cmp && !half && x < p.W, col, lo, (unsigned int)(((int64_t)c * p.H + R) * p.W + x),
+		sgh_compact(p, L, cmp && !half && x < p.W, col, lo, (unsigned int)(((int64_t)c * p.H + R) * p.W + x),
 				(int)L.nz[col], (int)L.ns[col], oob - (int)L.nz[col] - (int)L.ns[col], redo_count, redo_list);
 	const unsigned long long a = sgh_wave_sum(rlo), b = sgh_wave_sum(rhi);
 	if (lane == 0 && (a | b)) {
@@ -2041,11 +2005,11 @@ struct SghWgBarrier {
 	__device__ __forceinline__ void operator()() const { __syncthreads(); }
 	__device__ __forceinline__ void wait_prev() const { __syncthreads(); }
 };
-template <int NI, int BW = SghCfg<NI>::WAVES, class BAR = SghWgBarrier>
-__device__ __forceinline__ void sgh_clear(SghLds<NI> &L, bool wait_prev, const BAR &bar = BAR()) {
+template <int BW = SGH_WAVES, class BAR = SghWgBarrier>
+__device__ __forceinline__ void sgh_clear(SghLds &L, bool wait_prev, const BAR &bar = BAR()) {
 	if (wait_prev)
 		bar.wait_prev();	/* the previous tile's finish is done with L */
-	constexpr int NH = 2 * NI * SGH_HROWS * 64 / 4, NC = 128 * NI / 4, T = 64 * BW;
+	constexpr int NH = 2 * SGH_HROWS * 64 / 4, NC = 128 / 4, T = 64 * BW;
 	uint4 *h = (uint4 *)&L.h[0][0][0];
 	const uint4 z = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
@@ -2069,31 +2033,31 @@ __device__ __forceinline__ void sgh_clear(SghLds<NI> &L, bool wait_prev, const B
  * the binning.  No block is loaded twice.  Frames 0..15 (wave 0's first block) are the centre
  * sample: wave 0 sorts them and publishes the band starts through LDS while the other waves'
  * first blocks are in flight (one barrier, which also covers the clear). */
-template <bool EDGE, int NBUF, int NORM, int NI>
-__device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &ro, SghLds<NI> &L, const SghFrame &F,
-		int wave, int lane,
-		uint32_t (&lo2)[NI], uint32_t (&nonzero)[NI], uint32_t (&nsat)[NI], int &counted, bool wait_prev) {
+template <bool EDGE, int NBUF, int NORM>
+__device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &ro, SghLds &L, const SghFrame &F,
+		int wave, int lane, uint32_t (&lo2)[SGH_NP], uint32_t (&nonzero)[SGH_NP], uint32_t (&nsat)[SGH_NP],
+		int &counted, bool wait_prev) {
 	constexpr int M = 16;		/* frames per block */
-	constexpr int WAVES = SghCfg<NI>::WAVES;
+	constexpr int WAVES = SGH_WAVES;
 	constexpr int STEP = M * WAVES;
 	constexpr int AHEAD = NBUF * STEP;
 	const int N = p.N;
 	uint32_t *const h = &L.h[0][0][0];
 	const uint32_t l4 = (uint32_t)lane * 4u;
-	uint32_t buf[NBUF][M][NI], fix[NBUF][NI];
+	uint32_t buf[NBUF][M][SGH_NP], fix[NBUF][SGH_NP];
 	SghTab16 T;
-	auto loadblk = [&](int f0, uint32_t (&dst)[M][NI], uint32_t (&fx)[NI]) {
+	auto loadblk = [&](int f0, uint32_t (&dst)[M][SGH_NP], uint32_t (&fx)[SGH_NP]) {
 		if (f0 + M <= N)
-			sgh_loadblk<true, EDGE, NI>(F, T, N, f0, dst, fx);
+			sgh_loadblk<true, EDGE>(F, T, N, f0, dst, fx);
 		else
-			sgh_loadblk<false, EDGE, NI>(F, T, N, f0, dst, fx);
+			sgh_loadblk<false, EDGE>(F, T, N, f0, dst, fx);
 	};
 	int f[NBUF];
 #pragma unroll
 	for (int k = 0; k < NBUF; k++) {
 		f[k] = M * wave + k * STEP;
 #pragma unroll
-		for (int i = 0; i < NI; i++)
+		for (int i = 0; i < SGH_NP; i++)
 			fix[k][i] = 0;
 		if (f[k] < N) {
 			sgh_tab16(ro, f[k], T);
@@ -2103,7 +2067,7 @@ __device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &r
 	sgh_clear(L, wait_prev);
 	if (wave == 0) {
 #pragma unroll
-		for (int i = 0; i < NI; i++) {
+		for (int i = 0; i < SGH_NP; i++) {
 			uint32_t p16[SGH_CENTER];
 #pragma unroll
 			for (int m = 0; m < SGH_CENTER; m++) {
@@ -2121,15 +2085,15 @@ __device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &r
 	}
 	__syncthreads();	/* histogram cleared, band starts published */
 #pragma unroll
-	for (int i = 0; i < NI; i++)
+	for (int i = 0; i < SGH_NP; i++)
 		lo2[i] = L.lo2[i][lane];
 	const bool loads_only = SG_DBG(p) == 3;
-	auto binblk = [&](int f0, const uint32_t (&raw)[M][NI], const uint32_t (&fx)[NI]) {
+	auto binblk = [&](int f0, const uint32_t (&raw)[M][SGH_NP], const uint32_t (&fx)[SGH_NP]) {
 		if (loads_only) {
 #pragma unroll
 			for (int m = 0; m < M; m++)
 #pragma unroll
-				for (int i = 0; i < NI; i++)
+				for (int i = 0; i < SGH_NP; i++)
 					nonzero[i] ^= raw[m][i];
 		} else {
 #pragma unroll
@@ -2139,7 +2103,7 @@ __device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &r
 					if (NORM)
 						sgh_coef(ro, f0 + m, a, b);
 #pragma unroll
-					for (int i = 0; i < NI; i++) {
+					for (int i = 0; i < SGH_NP; i++) {
 						uint32_t v = sgh_fixup<EDGE>(raw[m][i], fx[i], m);
 						if (NORM)
 							v = sgh_norm_pair<NORM, EDGE>(v, a, b, fx[i], m);
@@ -2170,17 +2134,16 @@ __device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &r
 	}
 }
 
-/* the same build with 8-frame half blocks (the default for NI = 1, SGH_HALF1; NI = 2 loads
- * two dwords per lane and frame):
+/* the same build with 8-frame half blocks (the default, SGH_HALF1):
  * wave w bins the 16-frame blocks w, w + WAVES, ... in order, each as two halves; NB blocks
  * (2 NB half buffers) are in flight, so while one half is binned 2 NB - 1 halves keep
- * loading (with two 8-wave workgroups per CU, one workgroup's loads must carry the CU while
- * the other runs its finish).  The shift table of a block is fetched once for both halves.
+ * loading (of the four 4-wave workgroups on a CU, those still building must carry its loads
+ * while the others run their finish).  The shift table of a block is fetched once for both halves.
  * Wave 0's first block (frames 0..15) is the centre sample. */
 #ifndef SGH_NB
-#define SGH_NB 1	/* 2: 4.85 vs 4.62 ms (NI = 2, scripts/gpu_r2i.sh) */
+#define SGH_NB 1	/* blocks in flight per wave (2 measured equal, scripts/gpu_r2u.sh) */
 #endif
-/* NI = 1 also streams half blocks (scripts/gpu_r2u.sh, two alternating rounds on one box:
+/* half blocks against the 16-frame build (scripts/gpu_r2u.sh, two alternating rounds on one box:
  * 4.111-4.119 ms against 4.179-4.186 for the 16-frame build, NB = 1 and 2 equal; the 16-frame
  * build with a third buffer 4.23-4.24): the straight-line steady loop with sched_barriers keeps
  * every refill right behind its binning */
@@ -2198,9 +2161,9 @@ __device__ __forceinline__ void sgh_build(const SgStackParams &p, const SghRo &r
 #define SGH_WINS_ORDER 1	/* WINSORIZED finish: columns with zeros / 65535s first (sgh_tile) */
 #endif
 
-template <bool EDGE, int NORM, int NI, int NB, int BW = SghCfg<NI>::WAVES, class BAR = SghWgBarrier, bool AB = false>
-__device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const SghRo &ro, SghLds<NI> &L, const SghFrame &F,
-		int wave, int lane, uint32_t (&lo2)[NI], uint32_t (&nonzero)[NI], uint32_t (&nsat)[NI], int &counted,
+template <bool EDGE, int NORM, int NB, int BW = SGH_WAVES, class BAR = SghWgBarrier, bool AB = false>
+__device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const SghRo &ro, SghLds &L, const SghFrame &F,
+		int wave, int lane, uint32_t (&lo2)[SGH_NP], uint32_t (&nonzero)[SGH_NP], uint32_t (&nsat)[SGH_NP], int &counted,
 		bool wait_prev, const BAR &bar = BAR(), uint32_t *nab = nullptr) {
 	constexpr int MB = 8;
 	constexpr int WAVES = BW;	/* the waves building the tile */
@@ -2210,20 +2173,20 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 	const uint32_t l4 = (uint32_t)lane * 4u;
 	const uint32_t k1 = sgh_opaque(0x00010001u), ksat = sgh_opaque(0xFFFEFFFEu);
 	const uint32_t k255 = NORM && !AB ? sgh_opaque(0x00FF00FFu) : 0u;
-	uint32_t buf[NB][2][MB][NI], fix[NB][2][NI];
+	uint32_t buf[NB][2][MB][SGH_NP], fix[NB][2][SGH_NP];
 	SghTab16 T;
 	/* half hh (frames f16 + 8 hh ..) of the block at f16, bounds-checked unless whole */
-	auto loadh = [&](int f16, int hh, uint32_t (&dst)[MB][NI], uint32_t (&fx)[NI]) {
+	auto loadh = [&](int f16, int hh, uint32_t (&dst)[MB][SGH_NP], uint32_t (&fx)[SGH_NP]) {
 		if (f16 + 16 <= N) {
 			if (hh == 0)
-				sgh_loadblk<true, EDGE, NI, MB, 0>(F, T, N, f16, dst, fx);
+				sgh_loadblk<true, EDGE, MB, 0>(F, T, N, f16, dst, fx);
 			else
-				sgh_loadblk<true, EDGE, NI, MB, 8>(F, T, N, f16 + 8, dst, fx);
+				sgh_loadblk<true, EDGE, MB, 8>(F, T, N, f16 + 8, dst, fx);
 		} else {
 			if (hh == 0)
-				sgh_loadblk<false, EDGE, NI, MB, 0>(F, T, N, f16, dst, fx);
+				sgh_loadblk<false, EDGE, MB, 0>(F, T, N, f16, dst, fx);
 			else
-				sgh_loadblk<false, EDGE, NI, MB, 8>(F, T, N, f16 + 8, dst, fx);
+				sgh_loadblk<false, EDGE, MB, 8>(F, T, N, f16 + 8, dst, fx);
 		}
 	};
 	int f16 = 16 * wave;
@@ -2231,7 +2194,7 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 	for (int b = 0; b < NB; b++) {
 		const int fb = f16 + b * STEP;
 #pragma unroll
-		for (int i = 0; i < NI; i++)
+		for (int i = 0; i < SGH_NP; i++)
 			fix[b][0][i] = fix[b][1][i] = 0;
 		if (fb < N) {
 			sgh_tab16(ro, fb, T);
@@ -2239,7 +2202,7 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 			loadh(fb, 1, buf[b][1], fix[b][1]);
 		}
 	}
-	sgh_clear<NI, BW>(L, wait_prev, bar);
+	sgh_clear<BW>(L, wait_prev, bar);
 	const bool nocentre = SG_DBG(p) == 15;	/* A/B: loads only, no centre and no start barrier */
 	static_assert(!SGH_CENTER2W || SGH_CENTER == 2 * MB, "two half blocks make the centre sample");
 	if (SGH_CENTER2W && !nocentre) {
@@ -2248,7 +2211,7 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 		 * not wait for a second half block */
 		if (wave == 1) {
 #pragma unroll
-			for (int i = 0; i < NI; i++)
+			for (int i = 0; i < SGH_NP; i++)
 #pragma unroll
 				for (int m = 0; m < MB; m++) {
 					uint32_t v = sgh_fixup<EDGE>(buf[0][0][m][i], fix[0][0][i], m);
@@ -2263,7 +2226,7 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 		bar();
 		if (wave == 0) {
 #pragma unroll
-			for (int i = 0; i < NI; i++) {
+			for (int i = 0; i < SGH_NP; i++) {
 				uint32_t p16[SGH_CENTER];
 #pragma unroll
 				for (int m = 0; m < MB; m++) {
@@ -2282,7 +2245,7 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 		}
 	} else if (wave == 0 && !nocentre) {
 #pragma unroll
-		for (int i = 0; i < NI; i++) {
+		for (int i = 0; i < SGH_NP; i++) {
 			uint32_t p16[SGH_CENTER];
 #pragma unroll
 			for (int m = 0; m < SGH_CENTER; m++) {
@@ -2302,26 +2265,26 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 	if (!nocentre)
 		bar();	/* histogram cleared, band starts published */
 #pragma unroll
-	for (int i = 0; i < NI; i++)
+	for (int i = 0; i < SGH_NP; i++)
 		lo2[i] = nocentre ? 0u : L.lo2[i][lane];
-	uint32_t hi2[NI];	/* AB: lo + 255 per half (lo <= 65279: no carry between the halves) */
+	uint32_t hi2[SGH_NP];	/* AB: lo + 255 per half (lo <= 65279: no carry between the halves) */
 #pragma unroll
-	for (int i = 0; i < NI; i++)
+	for (int i = 0; i < SGH_NP; i++)
 		hi2[i] = lo2[i] + 0x00FF00FFu;
 	const bool loads_only = SG_DBG(p) == 3 || nocentre;
 	/* bin one half (frames f0 .. f0 + 7), per-frame bounds when it is not whole */
-	auto binh = [&](int f0, const uint32_t (&raw)[MB][NI], const uint32_t (&fx)[NI], bool whole) {
+	auto binh = [&](int f0, const uint32_t (&raw)[MB][SGH_NP], const uint32_t (&fx)[SGH_NP], bool whole) {
 		if (loads_only) {
 #pragma unroll
 			for (int m = 0; m < MB; m++)
 #pragma unroll
-				for (int i = 0; i < NI; i++)
+				for (int i = 0; i < SGH_NP; i++)
 					nonzero[i] ^= raw[m][i];
 		} else if (SGH_BIN2 && !NORM && !EDGE && whole) {
 #pragma unroll
 			for (int m = 0; m < MB; m += 2)
 #pragma unroll
-				for (int i = 0; i < NI; i++)
+				for (int i = 0; i < SGH_NP; i++)
 					sgh_bin_pair2<AB>(h + i * (2 * SGH_HROWS * 64), l4, lo2[i], raw[m][i], raw[m + 1][i], nonzero[i],
 							nsat[i], k1, ksat, AB ? nab + i : nullptr, hi2[i]);
 		} else {
@@ -2332,7 +2295,7 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 					if (NORM)
 						sgh_coef(ro, f0 + m, a, b);
 #pragma unroll
-					for (int i = 0; i < NI; i++) {
+					for (int i = 0; i < SGH_NP; i++) {
 						uint32_t v = sgh_fixup<EDGE>(raw[m][i], fx[i], m);
 						if (NORM)
 							v = sgh_norm_pair<NORM, EDGE>(v, a, b, fx[i], m);
@@ -2358,11 +2321,11 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 			sgh_tab16(ro, nx, T);
 			binh(fb, buf[b][0], fix[b][0], true);
 			__builtin_amdgcn_sched_barrier(0);
-			sgh_loadblk<true, EDGE, NI, MB, 0>(F, T, N, nx, buf[b][0], fix[b][0]);
+			sgh_loadblk<true, EDGE, MB, 0>(F, T, N, nx, buf[b][0], fix[b][0]);
 			__builtin_amdgcn_sched_barrier(0);
 			binh(fb + 8, buf[b][1], fix[b][1], true);
 			__builtin_amdgcn_sched_barrier(0);
-			sgh_loadblk<true, EDGE, NI, MB, 8>(F, T, N, nx + 8, buf[b][1], fix[b][1]);
+			sgh_loadblk<true, EDGE, MB, 8>(F, T, N, nx + 8, buf[b][1], fix[b][1]);
 			__builtin_amdgcn_sched_barrier(0);
 		}
 		f16 += NB * STEP;
@@ -2387,16 +2350,15 @@ __device__ __forceinline__ void sgh_build_half(const SgStackParams &p, const Sgh
 	}
 }
 
-/* REJ 2 = SIGMA, 4 = WINSORIZED; NORM 0 none, 1 additive, 2 multiplicative; NI pixel pairs
- * per lane (tile of 128 NI pixels, 4 NI waves).  Two 8-wave workgroups (69 KB of LDS each)
- * or four 4-wave ones (34.5 KB) per CU: 16 waves, at most 128 VGPRs. */
-/* one tile: bid = its index in (channel, row, 128 NI-column tile) order; wait_prev: a tile after
+/* REJ 2 = SIGMA, 4 = WINSORIZED; NORM 0 none, 1 additive, 2 multiplicative.  Four 4-wave
+ * workgroups (34.5 KB of LDS each) per CU: 16 waves, at most 128 VGPRs. */
+/* one tile: bid = its index in (channel, row, 128-column tile) order; wait_prev: a tile after
  * the first one of this workgroup, whose first frame loads may be issued while other waves of
  * the workgroup still finish the previous tile (the clear waits for them) */
-template <int REJ, int NORM, int NI>
-__device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro, SghLds<NI> &L, int bid, bool wait_prev,
+template <int REJ, int NORM>
+__device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro, SghLds &L, int bid, bool wait_prev,
 		unsigned int *__restrict__ redo_count, unsigned int *__restrict__ redo_list, int load = 0) {
-	constexpr int WAVES = SghW<REJ, NI>::WAVES, COLS = 128 * NI;
+	constexpr int WAVES = SGH_TILE_WAVES(REJ), COLS = 128;
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	const int ntx = (p.W + COLS - 1) / COLS;
@@ -2423,20 +2385,10 @@ __device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro
 
 	/* the histogram and the zero / 65535 counters are cleared by the build right after it has
 	 * issued its first frame loads (sgh_clear), and its start barrier covers the clear */
-	/* A/B timeline (SG_HIST_DBG=11, NI = 2): per tile, s_memrealtime (100 MHz) at entry,
-	 * after the build barrier and at the end of every wave's finish, written into the
-	 * output buffer as u64 [tile][4] (the image is garbage in this mode) */
-	uint64_t *const tl = (uint64_t *)p.out + (size_t)blockIdx.x * 32;
-	const bool timeline = NI == 2 && SG_DBG(p) == 11;
-	if (timeline && tid == 0) {
-		tl[0] = __builtin_amdgcn_s_memrealtime();
-		tl[3] = 0;
-	}
-
-	uint32_t nonzero[NI], nsat[NI], lo2[NI], nab[NI];
+	uint32_t nonzero[SGH_NP], nsat[SGH_NP], lo2[SGH_NP], nab[SGH_NP];
 	constexpr bool AB = REJ == 1 || REJ == 8;	/* stack_median / PERCENTILE: count the samples above the band */
 #pragma unroll
-	for (int i = 0; i < NI; i++)
+	for (int i = 0; i < SGH_NP; i++)
 		nonzero[i] = nsat[i] = nab[i] = 0;
 	int counted = 0;
 	/* the loading phase at a raised wave priority (SgStackParams::prio, default 1), so the
@@ -2457,46 +2409,46 @@ __device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro
 	rf.norm = ro.norm + ro.npad;
 	SghRo ri = ro;
 	ri.norm = ro.norm + 2 * ro.npad + 1;
-	if (NORMI && load == 2 && NI == 1 && !SGH_HALF1 && !AB) {
+	if (NORMI && load == 2 && !SGH_HALF1 && !AB) {
 		if (interior)
-			sgh_build<false, SGH_NBUF, 6, NI>(p, ri, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
+			sgh_build<false, SGH_NBUF, 6>(p, ri, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
 		else
-			sgh_build<true, SGH_NBUF, 6, NI>(p, ri, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
+			sgh_build<true, SGH_NBUF, 6>(p, ri, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
 	} else if (NORMI && load == 2) {
 		if (interior)
-			sgh_build_half<false, 6, NI, NI == 1 ? SGH_NB : SGH_NB2, WAVES, SghWgBarrier, AB>(p, ri, L, F, wave, lane,
+			sgh_build_half<false, 6, SGH_NB, WAVES, SghWgBarrier, AB>(p, ri, L, F, wave, lane,
 					lo2, nonzero, nsat, counted, wait_prev, SghWgBarrier(), nab);
 		else
-			sgh_build_half<true, 6, NI, NI == 1 ? SGH_NB : SGH_NB2, WAVES, SghWgBarrier, AB>(p, ri, L, F, wave, lane,
+			sgh_build_half<true, 6, SGH_NB, WAVES, SghWgBarrier, AB>(p, ri, L, F, wave, lane,
 					lo2, nonzero, nsat, counted, wait_prev, SghWgBarrier(), nab);
-	} else if (NORM >= 1 && NORM <= 3 && fma && NI == 1 && !SGH_HALF1 && !AB) {
+	} else if (NORM >= 1 && NORM <= 3 && fma && !SGH_HALF1 && !AB) {
 		if (interior)
-			sgh_build<false, SGH_NBUF, NF, NI>(p, rf, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
+			sgh_build<false, SGH_NBUF, NF>(p, rf, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
 		else
-			sgh_build<true, SGH_NBUF, NF, NI>(p, rf, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
+			sgh_build<true, SGH_NBUF, NF>(p, rf, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
 	} else if (NORM >= 1 && NORM <= 3 && fma) {
 		if (interior)
-			sgh_build_half<false, NF, NI, NI == 1 ? SGH_NB : SGH_NB2, WAVES, SghWgBarrier, AB>(p, rf, L, F, wave, lane,
+			sgh_build_half<false, NF, SGH_NB, WAVES, SghWgBarrier, AB>(p, rf, L, F, wave, lane,
 					lo2, nonzero, nsat, counted, wait_prev, SghWgBarrier(), nab);
 		else
-			sgh_build_half<true, NF, NI, NI == 1 ? SGH_NB : SGH_NB2, WAVES, SghWgBarrier, AB>(p, rf, L, F, wave, lane,
+			sgh_build_half<true, NF, SGH_NB, WAVES, SghWgBarrier, AB>(p, rf, L, F, wave, lane,
 					lo2, nonzero, nsat, counted, wait_prev, SghWgBarrier(), nab);
-	} else if (NI == 1 && !SGH_HALF1 && !AB) {
+	} else if (!SGH_HALF1 && !AB) {
 		if (interior)
-			sgh_build<false, SGH_NBUF, NORM, NI>(p, ro, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
+			sgh_build<false, SGH_NBUF, NORM>(p, ro, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
 		else
-			sgh_build<true, SGH_NBUF, NORM, NI>(p, ro, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
+			sgh_build<true, SGH_NBUF, NORM>(p, ro, L, F, wave, lane, lo2, nonzero, nsat, counted, wait_prev);
 	} else {
 		if (interior)
-			sgh_build_half<false, NORM, NI, NI == 1 ? SGH_NB : SGH_NB2, WAVES, SghWgBarrier, AB>(p, ro, L, F, wave, lane,
+			sgh_build_half<false, NORM, SGH_NB, WAVES, SghWgBarrier, AB>(p, ro, L, F, wave, lane,
 					lo2, nonzero, nsat, counted, wait_prev, SghWgBarrier(), nab);
 		else
-			sgh_build_half<true, NORM, NI, NI == 1 ? SGH_NB : SGH_NB2, WAVES, SghWgBarrier, AB>(p, ro, L, F, wave, lane,
+			sgh_build_half<true, NORM, SGH_NB, WAVES, SghWgBarrier, AB>(p, ro, L, F, wave, lane,
 					lo2, nonzero, nsat, counted, wait_prev, SghWgBarrier(), nab);
 	}
 	if (counted) {
 #pragma unroll
-		for (int i = 0; i < NI; i++) {
+		for (int i = 0; i < SGH_NP; i++) {
 			atomicAdd(&L.nz[128 * i + lane], (uint32_t)counted - (nonzero[i] & 0xFFFFu));
 			atomicAdd(&L.nz[128 * i + 64 + lane], (uint32_t)counted - (nonzero[i] >> 16));
 			atomicAdd(&L.ns[128 * i + lane], nsat[i] & 0xFFFFu);
@@ -2508,14 +2460,15 @@ __device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro
 		}
 	}
 	__syncthreads();
-	if (timeline && tid == 0)
-		tl[1] = __builtin_amdgcn_s_memrealtime();
 	if (p.prio == 3)
 		__builtin_amdgcn_s_setprio(1);	/* A/B: the finish raised instead */
 	else if (p.prio)
 		__builtin_amdgcn_s_setprio(0);
-	/* column col = 64 g + l of the tile: pixel pair i = g >> 1 of lane l, half g & 1, i.e.
-	 * image column x0 + 128 i + 2 l + (g & 1); its band start is the half of lo2[i][l] */
+	/* column col = 64 g + l of the tile: half g of lane l's pixel pair, i.e. image column
+	 * x0 + 2 l + g; its band start is that half of lo2[l].  col < 128, so col >> 7 is 0: the
+	 * term stays because without it (3 to 5 instructions fewer) the compiler orders the
+	 * WINSORIZED and SIGMEDIAN finishes differently and they measured 0.2-0.9 % slower
+	 * (profiles/r18_ab_retire_variants.log) */
 	auto col_x = [&](int col) { return x0 + 128 * (col >> 7) + 2 * (col & 63) + ((col >> 6) & 1); };
 	auto col_lo = [&](int col) { return (int)((L.lo2[col >> 7][col & 63] >> (16 * ((col >> 6) & 1))) & 0xFFFFu); };
 	if (REJ == 4) {
@@ -2526,41 +2479,7 @@ __device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro
 		 * ~3 (scripts/wins_predict.py, profiles/r02z_wins_predict.log), so those columns are
 		 * finished by wave 0 first and the rest after them (the sum of the two waves' maxima
 		 * 26.4 -> 21.5 iterations per tile on configs[4]'s data) */
-		if (NORM == 0 && NI == 1 && p.wx) {
-			/* SG_WINS_EXPORT: a column holding a zero or a 65535 sample needs ~10 inner iterations
-			 * against ~3 and holds its wave for them; it leaves the tile as its histogram (a slot per
-			 * column, one atomic per wave) and k_hist_slow finishes it among columns of its own kind.
-			 * The tile's waves finish the rest (a column without a slot is finished here) */
-			if (wave >= 2)
-				return;
-			const int col = 64 * wave + lane;
-			const int x = col_x(col);
-			const uint32_t nout = L.nz[col] + L.ns[col];
-			const bool slow = x < p.W && nout != 0u && nout <= (uint32_t)p.wx_kmax;
-			const uint64_t m = __ballot(slow);
-			unsigned int base = 0;
-			if (m) {
-				if (lane == 0)
-					base = atomicAdd(p.wx_count, (unsigned int)__popcll(m));
-				base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
-			}
-			const unsigned int slot = base + (unsigned int)__popcll(m & ((1ull << lane) - 1ull));
-			const bool out = slow && slot < p.wx_cap;
-			if (out) {
-				const uint32_t *hc = &L.h[col >> 6][0][col & 63];
-				const size_t cap = p.wx_cap;
-#pragma unroll 5
-				for (int j = 0; j < SGH_HROWS; j++)
-					p.wx[(size_t)j * cap + slot] = hc[64 * j];
-				p.wx[(size_t)SGH_HROWS * cap + slot] = (uint32_t)col_lo(col);
-				p.wx[(size_t)(SGH_HROWS + 1) * cap + slot] = L.nz[col] | (L.ns[col] << 16);
-				p.wx[(size_t)(SGH_HROWS + 2) * cap + slot] = (uint32_t)(((int64_t)c * p.H + R) * p.W + x);
-			}
-			sgh_finish2<REJ, false, NI, false, false>(p, L, col, 0, col_lo(col), R, c, out ? p.W : x, redo_count,
-					redo_list);
-			return;
-		}
-		if (SGH_WINS_ORDER && NI == 1) {
+		if (SGH_WINS_ORDER) {
 			if (wave == 0) {
 				const int ca = lane, cb = 64 + lane;
 				const bool sa = (L.nz[ca] | L.ns[ca]) != 0u, sb = (L.nz[cb] | L.ns[cb]) != 0u;
@@ -2575,68 +2494,61 @@ __device__ __forceinline__ void sgh_tile(const SgStackParams &p, const SghRo &ro
 			if (wave >= 2)
 				return;
 			const int col = L.perm[64 * wave + lane];
-			sgh_finish2<REJ, false, NI, NORM == 1 || NORM == 3, NORM != 0>(p, L, col, 0, col_lo(col), R, c, col_x(col),
+			sgh_finish2<REJ, false, NORM == 1 || NORM == 3, NORM != 0>(p, L, col, 0, col_lo(col), R, c, col_x(col),
 					redo_count, redo_list, interior);
 			return;
 		}
 		for (int col = 64 * wave + lane; col < COLS; col += 64 * WAVES)
-			sgh_finish2<REJ, false, NI, NORM == 1 || NORM == 3, NORM != 0>(p, L, col, 0, col_lo(col), R, c, col_x(col),
+			sgh_finish2<REJ, false, NORM == 1 || NORM == 3, NORM != 0>(p, L, col, 0, col_lo(col), R, c, col_x(col),
 					redo_count, redo_list, interior);
 		return;
 	}
 	if (REJ == 3) {	/* SIGMEDIAN: one lane per column (waves 0 and 1) */
 		for (int col = 64 * wave + lane; col < COLS; col += 64 * WAVES)
-			sgh_finish2<REJ, false, NI, false, false>(p, L, col, 0, col_lo(col), R, c, col_x(col), redo_count, redo_list);
+			sgh_finish2<REJ, false>(p, L, col, 0, col_lo(col), R, c, col_x(col), redo_count, redo_list);
 		return;
 	}
 	/* every wave finishes 32 pixel columns, a lane pair per column */
 	const int half = lane & 1;
 	int col = 32 * wave + (lane >> 1);
 	for (; col < COLS; col += 32 * WAVES)
-		sgh_finish2<REJ, true, NI, NORM == 1 || NORM == 3 || NORM == 4, NORM != 0 && REJ == 2>(p, L, col, half, col_lo(col), R, c,
+		sgh_finish2<REJ, true, NORM == 1 || NORM == 3, NORM != 0 && REJ == 2>(p, L, col, half, col_lo(col), R, c,
 				col_x(col), redo_count, redo_list, interior);
-	if (timeline && lane == 0) {
-		const uint64_t t = __builtin_amdgcn_s_memrealtime();
-		if (wave == 0)
-			tl[2] = t;
-		atomicMax((unsigned long long *)&tl[3], (unsigned long long)t);
-	}
 }
 
 /* REJ 2 = SIGMA, 4 = WINSORIZED; NORM 0 none, 1 additive, 2 multiplicative, 3 additive with the
- * folded + 0.5; NI pixel pairs per lane (tile of 128 NI pixels, 4 NI waves).  Two 8-wave
- * workgroups (69 KB of LDS each) or four 4-wave ones (36 KB) per CU: 16 waves, at most 128
+ * folded + 0.5.  Four 4-wave workgroups (36 KB of LDS each) per CU: 16 waves, at most 128
  * VGPRs. */
 #ifndef SGH_WINS_WPE
 #define SGH_WINS_WPE 2	/* WINSORIZED: waves per SIMD the register budget is sized for (2-wave tiles: 4 tiles per CU, the LDS limit; 4 waves per SIMD = 128 VGPRs spill) */
 #endif
-template <int REJ, int NORM, int NI>
-__global__ void __launch_bounds__((64 * SghW<REJ, NI>::WAVES), ((REJ == 4 && NI == 1) ? SGH_WINS_WPE : SghCfg<NI>::WPE))
+template <int REJ, int NORM>
+__global__ void __launch_bounds__((64 * SGH_TILE_WAVES(REJ)), (REJ == 4 ? SGH_WINS_WPE : SGH_WPE))
 k_stack_hist(SgStackParams p, const int *__restrict__ tab, const int4 *__restrict__ norm,
 		unsigned int *__restrict__ redo_count, unsigned int *__restrict__ redo_list) {
 	SghRo ro;
 	ro.tab = tab;
 	ro.norm = norm;
 	ro.npad = p.hist_npad;
-	__shared__ SghLds<NI> L;
+	__shared__ SghLds L;
 	/* XCD-aware tile order: the dispatcher deals workgroups round-robin to the 8 XCDs, so
 	 * XCD k gets a contiguous run of tiles (whole rows: neighbouring tiles share the 128-B
 	 * lines their shifted rows straddle in that XCD's L2, and the slower image-edge tiles
 	 * spread evenly instead of all landing on XCDs 0 and 7) */
 	const int nblk = (int)gridDim.x, xcd = (int)blockIdx.x & 7, q = nblk >> 3, rem = nblk & 7;
 	const int vb = xcd * q + (xcd < rem ? xcd : rem) + ((int)blockIdx.x >> 3);
-	const int ntiles = ((p.W + 128 * NI - 1) / (128 * NI)) * (p.row_end - p.row_begin) * p.C;
+	const int ntiles = ((p.W + 127) / 128) * (p.row_end - p.row_begin) * p.C;
 	/* one tile per workgroup: stacking 2 or 4 consecutive tiles per workgroup (the next
 	 * tile's first loads overlapping the previous finish) measured 5.0 / 4.9 ms against 3.58
 	 * (scripts/gpu_r3p.sh; the tile loop also costs registers: 128 VGPRs + scratch) */
 	if (vb >= ntiles)
 		return;
 	/* normalised: the single-rounding load when k_norm_fma_check found it exact for every frame (its
-	 * flag word behind the pairs stays 0; the host stages 1 when the check is not run) */
+	 * flag word behind the pairs stays 0; the host stages 3 when the check is not run) */
 	const unsigned int verdict = NORM >= 1 && NORM <= 3 ? ((const unsigned int *)(norm + 2 * ro.npad))[0] : 3u;
 	/* 1: single rounding (fma), 2: integer offset (additive, scale 1), 0: the reference's operations */
 	const int load = (NORM == 1 || NORM == 3) && !(verdict & 2u) ? 2 : (!(verdict & 1u) ? 1 : 0);
-	sgh_tile<REJ, NORM, NI>(p, ro, L, vb, false, redo_count, redo_list, load);
+	sgh_tile<REJ, NORM>(p, ro, L, vb, false, redo_count, redo_list, load);
 }
 
 /* k_norm_fma_check: may the normalising load use one fma per sample?  The reference normalises
@@ -2697,92 +2609,48 @@ k_norm_fma_check(double *__restrict__ pairs, int N, int npad, int mode, unsigned
 	}
 }
 
-/* k_hist_slow: the exported WINSORIZED columns (SgStackParams::wx), 64 per wave, each lane's
- * histogram column back in LDS in the tile's layout, finished by the tile's own code (sgh_finish2:
- * the same queries, decisions, redo list and counters).  Waves of exported columns only: their
- * inner-iteration counts are alike, and no build shares the CU's LDS with them. */
-struct SghSlowLds {
-	uint32_t h[1][SGH_HROWS][64];
-	uint32_t nz[64], ns[64], na[64];
-};
-#ifndef SGH_SLOW_WPE
-#define SGH_SLOW_WPE 2
-#endif
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SGH_SLOW_WPE)))
-k_hist_slow(SgStackParams p, unsigned int *__restrict__ redo_count, unsigned int *__restrict__ redo_list) {
-	__shared__ SghSlowLds L;
-	const int lane = threadIdx.x & 63;
-	const unsigned int cnt = *(volatile const unsigned int *)p.wx_count;
-	const unsigned int n = cnt < p.wx_cap ? cnt : p.wx_cap;
-	const size_t cap = p.wx_cap;
-	for (unsigned int s0 = blockIdx.x * 64u; s0 < n; s0 += gridDim.x * 64u) {
-		const unsigned int slot = s0 + (unsigned int)lane;
-		const bool v = slot < n;
-#pragma unroll 5
-		for (int j = 0; j < SGH_HROWS; j++)
-			L.h[0][j][lane] = v ? p.wx[(size_t)j * cap + slot] : 0u;
-		const uint32_t lo = v ? p.wx[(size_t)SGH_HROWS * cap + slot] : 1u;
-		const uint32_t zs = v ? p.wx[(size_t)(SGH_HROWS + 1) * cap + slot] : 0u;
-		const uint32_t pix = v ? p.wx[(size_t)(SGH_HROWS + 2) * cap + slot] : 0u;
-		L.nz[lane] = zs & 0xFFFFu;
-		L.ns[lane] = zs >> 16;
-		L.na[lane] = 0u;
-		const uint32_t W = (uint32_t)p.W, t = pix / W;
-		const int x = v ? (int)(pix - t * W) : p.W;
-		const int R = (int)(t % (uint32_t)p.H), c = (int)(t / (uint32_t)p.H);
-		/* each lane reads only its own column: no barrier */
-		sgh_finish2<4, false, 1, false, false, SghSlowLds>(p, L, lane, 0, (int)lo, R, c, x, redo_count, redo_list);
-	}
-}
-
-template __global__ void k_stack_hist<2, 0, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<2, 0>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<2, 1, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<2, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<2, 2, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<2, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<2, 3, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<2, 3>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<4, 3, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<4, 3>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<4, 0, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<4, 0>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<4, 1, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<4, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<4, 2, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<4, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<1, 0, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<1, 0>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<1, 1, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<1, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<1, 2, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<1, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<1, 3, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<1, 3>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<3, 0, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<3, 0>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<3, 1, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<3, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<3, 2, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<3, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<3, 3, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<3, 3>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<8, 0, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<8, 0>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<8, 1, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<8, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<8, 2, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<8, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
-template __global__ void k_stack_hist<8, 3, 1>(SgStackParams, const int *, const int4 *, unsigned int *,
-		unsigned int *);
-template __global__ void k_stack_hist<2, 0, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
-		unsigned int *);
-template __global__ void k_stack_hist<4, 0, 2>(SgStackParams, const int *, const int4 *, unsigned int *,
+template __global__ void k_stack_hist<8, 3>(SgStackParams, const int *, const int4 *, unsigned int *,
 		unsigned int *);
 
 /* threads per histogram workgroup (the host's launch shape) */
-int sgh_block_threads(int ni, int rej) {
-	if (rej == 4)
-		return ni == 2 ? 64 * SghW<4, 2>::WAVES : 64 * SghW<4, 1>::WAVES;
-	return ni == 2 ? 64 * SghCfg<2>::WAVES : 64 * SghCfg<1>::WAVES;
+int sgh_block_threads(int rej) {
+	return 64 * SGH_TILE_WAVES(rej);
 }

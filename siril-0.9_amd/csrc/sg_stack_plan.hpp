@@ -125,8 +125,8 @@ enum SgMainPath {
 	SG_MAIN_REDUCE2,	/* k_stack_reduce2: a pixel pair per lane */
 	SG_MAIN_REDUCE3,	/* k_stack_reduce3<m, seg>: XCD-aware SGPR-offset loads */
 	SG_MAIN_SORTED,		/* k_stack_sorted<nreg, false> over every tile */
-	SG_MAIN_HIST,		/* k_stack_hist<rj, norm, ni> */
-	SG_MAIN_LINFIT,		/* k_stack_linfit<km, nw, pair> */
+	SG_MAIN_HIST,		/* k_stack_hist<rj, norm> */
+	SG_MAIN_LINFIT,		/* k_stack_linfit<km, nw> */
 	SG_MAIN_LITERAL_ALL,	/* k_list_all: every pixel to the literal kernel */
 	SG_MAIN_REDUCE_WIDE	/* k_stack_reduce_wide: SUM / MEAN of more than SG_SUM_U32_MAXN frames, 64-bit sums */
 };
@@ -169,18 +169,16 @@ struct SgStackPlan {
 	bool sum;			/* SUM: the raw sums and the maximum */
 	bool wide;			/* SUM / MEAN without rejection past SG_SUM_U32_MAXN frames: 64-bit sums and maximum */
 	int main;			/* SgMainPath */
-	int nreg, rj, norm, ni, km, nw, seg, m;
-	bool pair;
+	int nreg, rj, norm, km, nw, seg, m;
 	bool linfit_tables;		/* k_linfit_tables runs first */
 	bool norm_check;		/* k_norm_fma_check runs before the main kernel */
-	bool compact, wexp;
-	size_t cmp_cap, wx_cap;
-	int wx_kmax;
+	bool compact;
+	size_t cmp_cap;
 	int redo;			/* SgRedoRoute */
 	unsigned int list_minn, rp_maxn;	/* SG_REDO_REPLAY_MAX on the replay route, else 0 */
 	int replay_nm;			/* k_stack_replay<replay_nm> runs (0: it does not) */
 	/* launch shapes */
-	unsigned int main_grid[3], main_threads;	/* main_threads 0: sgh_block_threads(ni, rj) */
+	unsigned int main_grid[3], main_threads;	/* main_threads 0: sgh_block_threads(rj) */
 	size_t main_lds, sorted_lds;
 	unsigned int fin_grid_x;	/* k_sum_finalize: (fin_grid_x, rows, C) */
 	size_t npix_img, npix_launch;
@@ -273,8 +271,7 @@ static void sg_plan_norm_table(const sg_stack_desc *d, const SgKnobs &k, SgStack
 	/* the word k_norm_fma_check starts from (bit 0: no fma load, bit 1: no integer load; the check
 	 * ORs in what it finds) and the histogram kernel reads as the load verdict.  This is the one
 	 * place it is computed: SG_NORM_FMA 0 -> 3 (neither form; the check does not run), 1 -> 2 (the
-	 * fma only), 2 (default) -> 0 (the integer form first).  The kernel-side comment in
-	 * sg_stack_hist.hip ("the host stages 1 when the check is not run") is wrong: it is 3 */
+	 * fma only), 2 (default) -> 0 (the integer form first) */
 	pl.staged_verdict = k.norm_fma == 0 ? 3u : (k.norm_fma == 1 ? 2u : 0u);
 	if (!pl.normalize)
 		return;
@@ -424,19 +421,15 @@ static int sg_plan_blocks(const sg_stack_desc *d, SgStackPlan &pl) {
 	return SG_OK;
 }
 
-/* the histogram main kernel's template arguments, its compact / export side lists and the
+/* the histogram main kernel's template arguments, its compact side list and the
  * load check */
 static void sg_plan_hist(const SgKnobs &k, SgStackPlan &pl) {
 	const int N = pl.N, W = pl.W, C = pl.C, nrows = pl.nrows;
-	const bool sigma_wins = pl.method == SG_STACK_MEAN && (pl.rejection == SG_SIGMA || pl.rejection == SG_WINSORIZED);
 	/* REJ: 2 SIGMA, 4 WINSORIZED, 1 PERCENTILE, 3 SIGMEDIAN, 8 stack_median */
 	pl.rj = pl.method == SG_STACK_MEDIAN ? 8 : pl.rejection == SG_WINSORIZED ? 4 :
 		pl.rejection == SG_PERCENTILE ? 1 : pl.rejection == SG_SIGMEDIAN ? 3 : 2;
-	/* tile = 128 NI pixels of a row, 4 NI waves: NI = 1 by default (sg_stack_hist.hip);
-	 * the A/B NI = 2 (SG_HIST_NI=2) exists without normalisation only (it spills there:
-	 * the per-sample double arithmetic of two pixel pairs) */
-	pl.ni = (pl.norm == 0 && k.hist_ni == 2 && sigma_wins) ? 2 : 1;
-	pl.main_grid[0] = (unsigned)((size_t)((W + 128 * pl.ni - 1) / (128 * pl.ni)) * nrows * C);
+	/* a tile = 128 pixels of a row (sg_stack_hist.hip) */
+	pl.main_grid[0] = (unsigned)((size_t)((W + 127) / 128) * nrows * C);
 	pl.main_threads = 0;
 	pl.main_lds = (size_t)k.hist_ldspad;
 	/* normalised SIGMA / WINSORIZED: redo pixels whose samples the tile fully knows leave
@@ -445,13 +438,6 @@ static void sg_plan_hist(const SgKnobs &k, SgStackPlan &pl) {
 	if (pl.compact)
 		pl.cmp_cap = std::min<size_t>(pl.npix_launch, k.hist_compact >= 2 ?
 				(size_t)k.hist_compact : ((size_t)384 << 20) / ((size_t)N * 2));
-	/* WINSORIZED without normalisation: the slow columns (a zero or a 65535 sample) leave their
-	 * tiles for k_hist_slow (SG_WINS_EXPORT), up to a quarter of the launch's pixels */
-	pl.wexp = pl.rj == 4 && pl.norm == 0 && pl.ni == 1 && k.wins_export;
-	if (pl.wexp) {
-		pl.wx_cap = ((pl.npix_launch / 4 + 63) / 64) * 64;
-		pl.wx_kmax = k.wins_export;
-	}
 	/* normalised: check the single-rounding load against the reference's operations over every
 	 * u16 value of every frame (k_norm_fma_check, ~10 us); the kernel reads the verdict.
 	 * norm_fma: the best load allowed; the verdict replaces it when the call is folded */
@@ -466,8 +452,6 @@ static void sg_plan_linfit(const SgKnobs &k, SgStackPlan &pl) {
 	pl.km = pl.N <= 512 ? 8 : 16;
 	/* waves per tile: 4, 8 or (KM = 8 only: 187 VGPRs at KM = 16) 16 */
 	pl.nw = k.linfit_waves == 4 ? 4 : (k.linfit_waves == 16 && pl.km == 8) ? 16 : 8;
-	/* SG_LINFIT_PAIR: both pixels of a sorted pair in lockstep (lfx_pixel2_m), 4 or 8 waves */
-	pl.pair = k.linfit_pair && pl.nw != 16;
 	pl.main_grid[0] = (unsigned)((size_t)((pl.W + 63) / 64) * pl.nrows * pl.C);
 	pl.main_threads = 64u * pl.nw;
 	pl.main_lds = (size_t)64 * (64 * pl.km + 2) * sizeof(uint16_t);
@@ -608,7 +592,6 @@ static int sg_stack_plan(const sg_stack_desc *d, int row_begin, int row_end, con
 	pl.npix_img = (size_t)pl.C * pl.H * pl.W;
 	pl.rejection_family = d->method == SG_STACK_MEDIAN || (d->method == SG_STACK_MEAN && d->rejection != SG_NO_REJEC);
 	pl.sum = d->method == SG_STACK_SUM;
-	pl.ni = 1;
 	pl.main_grid[0] = pl.main_grid[1] = pl.main_grid[2] = 1;
 	if (int rc = sg_plan_residency(d, pl))
 		return rc;

@@ -261,7 +261,7 @@ static void test_route_n15_n16(void) {
 		CHECK(a.pl.redo == SG_REDO_NONE && a.pl.main_kernel_blocks == 4 * 8 && a.pl.main_grid[0] == 32);
 		CHECK(a.pl.main_lds == (size_t)15 * 66 * 2 && a.pl.main_threads == 256);
 		Case b(method, r, 16);
-		CHECK(b.plan() == SG_OK && b.pl.main == SG_MAIN_HIST && b.pl.rj == rj[i] && b.pl.norm == 0 && b.pl.ni == 1);
+		CHECK(b.plan() == SG_OK && b.pl.main == SG_MAIN_HIST && b.pl.rj == rj[i] && b.pl.norm == 0);
 		CHECK(b.pl.path == 1 && b.pl.main_grid[0] == 2 * 8 && b.pl.main_kernel_blocks == 4 * 8 && b.pl.main_lds == 0);
 		/* launches: main, redo, the replay (SIGMA / WINSORIZED only), two literal phases */
 		CHECK(b.pl.launches == (i < 2 ? 5 : 4));
@@ -288,19 +288,17 @@ static void test_route_linfit(void) {
 	for (int N : {16, 512, 513, 1024}) {
 		const int km = N <= 512 ? 8 : 16;
 		Case c(SG_STACK_MEAN, SG_LINEARFIT, N);
-		CHECK(c.plan() == SG_OK && c.pl.main == SG_MAIN_LINFIT && c.pl.km == km && c.pl.nw == 8 && !c.pl.pair);
+		CHECK(c.plan() == SG_OK && c.pl.main == SG_MAIN_LINFIT && c.pl.km == km && c.pl.nw == 8);
 		CHECK(c.pl.path == 1 && c.pl.redo == SG_REDO_SORTED && c.pl.replay_nm == 0 && c.pl.linfit_tables);
 		CHECK(c.pl.main_grid[0] == 4 * 8 && c.pl.main_threads == 512);
-		CHECK(c.pl.main_lds == (size_t)64 * (64 * km + 2) * 2 && c.pl.launches == 4 && !c.pl.compact && !c.pl.wexp);
+		CHECK(c.pl.main_lds == (size_t)64 * (64 * km + 2) * 2 && c.pl.launches == 4 && !c.pl.compact);
 		CHECK(c.pl.sorted_lds == (size_t)N * 66 * 2 + (size_t)64 * ((N + 31) / 32) * 4);
 		c.k.linfit_waves = 4;
 		CHECK(c.plan() == SG_OK && c.pl.nw == 4 && c.pl.main_threads == 256);
-		c.k.linfit_pair = 1;
-		CHECK(c.plan() == SG_OK && c.pl.nw == 4 && c.pl.pair);
 		c.k.linfit_waves = 16;
-		CHECK(c.plan() == SG_OK && c.pl.nw == (km == 8 ? 16 : 8) && c.pl.pair == (km != 8));
+		CHECK(c.plan() == SG_OK && c.pl.nw == (km == 8 ? 16 : 8));
 		c.k.linfit_waves = 12;
-		CHECK(c.plan() == SG_OK && c.pl.nw == 8 && c.pl.pair);
+		CHECK(c.plan() == SG_OK && c.pl.nw == 8);
 	}
 	Case a(SG_STACK_MEAN, SG_LINEARFIT, 15);
 	CHECK(a.plan() == SG_OK && a.pl.main == SG_MAIN_SORTED && a.pl.linfit_tables);
@@ -399,19 +397,15 @@ static void test_route_norm(void) {
 			CHECK(r.plan() == SG_OK && r.pl.normalize == 0 && r.pl.nm.empty());
 		}
 	}
-	/* NI = 2: the knob, no normalisation, SIGMA / WINSORIZED */
+	/* 128-pixel tiles: W = 300 is 3 tiles a row, plain and normalised */
 	for (int rej : {SG_SIGMA, SG_WINSORIZED, SG_PERCENTILE, SG_SIGMEDIAN}) {
 		Case c(SG_STACK_MEAN, rej, 16, 300);
-		CHECK(c.plan() == SG_OK && c.pl.ni == 1 && c.pl.main_grid[0] == 3 * 8);
-		c.k.hist_ni = 2;
-		const int ni = rej == SG_SIGMA || rej == SG_WINSORIZED ? 2 : 1;
-		CHECK(c.plan() == SG_OK && c.pl.ni == ni && c.pl.main_grid[0] == (ni == 2 ? 2u * 8 : 3u * 8));
+		CHECK(c.plan() == SG_OK && c.pl.main_grid[0] == 3 * 8);
 		c.norm(SG_ADDITIVE);
-		CHECK(c.plan() == SG_OK && c.pl.ni == 1);
+		CHECK(c.plan() == SG_OK && c.pl.main_grid[0] == 3 * 8);
 	}
-	Case m(SG_STACK_MEDIAN, SG_NO_REJEC, 16);
-	m.k.hist_ni = 2;
-	CHECK(m.plan() == SG_OK && m.pl.ni == 1);
+	Case m(SG_STACK_MEDIAN, SG_NO_REJEC, 16, 300);
+	CHECK(m.plan() == SG_OK && m.pl.main_grid[0] == 3 * 8);
 	/* the staged verdict word and the load check */
 	const unsigned int staged[3] = {3, 2, 0};
 	for (int knob = 0; knob < 3; knob++)
@@ -430,7 +424,7 @@ static void test_route_norm(void) {
 	CHECK(u.plan() == SG_OK && !u.pl.norm_check && u.pl.norm_fma == 0);
 }
 
-static void test_route_compact_export(void) {
+static void test_route_compact(void) {
 	for (int rej : {SG_SIGMA, SG_WINSORIZED, SG_PERCENTILE, SG_SIGMEDIAN})
 		for (int mode : {SG_NO_NORM, SG_ADDITIVE, SG_MULTIPLICATIVE}) {
 			const bool on = (rej == SG_SIGMA || rej == SG_WINSORIZED) && mode != SG_NO_NORM;
@@ -443,18 +437,7 @@ static void test_route_compact_export(void) {
 			CHECK(c.plan() == SG_OK && c.pl.compact == on && c.pl.cmp_cap == (on ? 5u : 0u));
 			c.k.hist_compact = 0;
 			CHECK(c.plan() == SG_OK && !c.pl.compact);
-			/* WINSORIZED without normalisation, NI = 1, the knob */
-			c.k.wins_export = 3;
-			const bool ex = rej == SG_WINSORIZED && mode == SG_NO_NORM;
-			CHECK(c.plan() == SG_OK && c.pl.wexp == ex && c.pl.wx_cap == (ex ? 512u : 0u) && c.pl.wx_kmax == (ex ? 3 : 0));
-			c.k.hist_ni = 2;
-			CHECK(c.plan() == SG_OK && !c.pl.wexp);
 		}
-	Case x(SG_STACK_MEAN, SG_WINSORIZED, 16, 65, 6);	/* 390 pixels: a quarter, rounded up to 64 */
-	x.k.wins_export = 1;
-	CHECK(x.plan() == SG_OK && x.pl.wexp && x.pl.wx_cap == 128);
-	x.k.wins_export = 0;
-	CHECK(x.plan() == SG_OK && !x.pl.wexp);
 	Case big(SG_STACK_MEAN, SG_SIGMA, 16, 4096, 4096);	/* 16.7 M pixels against 384 MiB / 32 B */
 	big.norm(SG_ADDITIVE);
 	CHECK(big.plan() == SG_OK && big.pl.compact && big.pl.cmp_cap == ((size_t)384 << 20) / 32);
@@ -588,7 +571,44 @@ static void test_params(void) {
 	CHECK(c.pl.sh[48 + 4] == -7 && c.pl.sh[48 + 20 + 4] == 2);
 }
 
+/* the knobs of the removed A/B paths (256-pixel tiles, exported Winsorize columns, LINEARFIT
+ * lockstep pairs) are no longer read: with them set, the plans equal those of a clean environment.
+ * same_plan lists the route and launch fields by hand: a field added to SgStackPlan belongs here too */
+static bool same_plan(const SgStackPlan &a, const SgStackPlan &b) {
+	return a.main == b.main && a.rj == b.rj && a.norm == b.norm && a.nreg == b.nreg && a.km == b.km && a.nw == b.nw &&
+		a.main_grid[0] == b.main_grid[0] && a.main_grid[1] == b.main_grid[1] && a.main_grid[2] == b.main_grid[2] &&
+		a.main_threads == b.main_threads && a.main_lds == b.main_lds && a.sorted_lds == b.sorted_lds &&
+		a.launches == b.launches && a.main_kernel_blocks == b.main_kernel_blocks && a.path == b.path &&
+		a.compact == b.compact && a.cmp_cap == b.cmp_cap && a.redo == b.redo && a.rp_maxn == b.rp_maxn &&
+		a.list_minn == b.list_minn && a.replay_nm == b.replay_nm && a.linfit_tables == b.linfit_tables &&
+		a.norm_check == b.norm_check && a.scratch_bytes == b.scratch_bytes && a.npix_launch == b.npix_launch &&
+		a.sh == b.sh && a.nm == b.nm && a.tables == b.tables && a.ztab == b.ztab;
+}
+static void test_removed_knobs(void) {
+	const char *names[3] = {"SG_HIST_NI", "SG_WINS_EXPORT", "SG_LINFIT_PAIR"};
+	const int rej[3] = {SG_SIGMA, SG_WINSORIZED, SG_LINEARFIT};
+	for (int i = 0; i < 3; i++) {
+		for (const char *n : names)
+			unsetenv(n);
+		Case clean(SG_STACK_MEAN, rej[i], 16, 300);
+		clean.k.read();
+		CHECK(clean.plan() == SG_OK);
+		setenv("SG_HIST_NI", "2", 1);
+		setenv("SG_WINS_EXPORT", "1", 1);
+		setenv("SG_LINFIT_PAIR", "1", 1);
+		Case set(SG_STACK_MEAN, rej[i], 16, 300);
+		set.k.read();
+		CHECK(set.plan() == SG_OK);
+		CHECK(same_plan(clean.pl, set.pl));
+		CHECK(set.pl.main == (rej[i] == SG_LINEARFIT ? SG_MAIN_LINFIT : SG_MAIN_HIST));
+		CHECK(set.pl.main_grid[0] == (rej[i] == SG_LINEARFIT ? 5u * 8 : 3u * 8));
+	}
+	for (const char *n : names)
+		unsetenv(n);
+}
+
 int main(int argc, char **argv) {
+	test_removed_knobs();
 	test_chain_tables();
 	test_additive_fold(argc > 1 ? atoi(argv[1]) : 200);
 	test_ztab();
@@ -598,7 +618,7 @@ int main(int argc, char **argv) {
 	test_route_replay();
 	test_route_addresses();
 	test_route_norm();
-	test_route_compact_export();
+	test_route_compact();
 	test_route_reduce();
 	test_errors();
 	test_params();
