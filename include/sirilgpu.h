@@ -508,6 +508,50 @@ int sg_findstar_fit_device(sg_ctx *ctx, int dev_index, const sg_starfit_desc *de
 int sg_findstar_fit(sg_ctx *ctx, const sg_starfit_desc *desc, const uint16_t *frames, int nframes,
 		sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars, sg_starfit_cand *cands);
 
+/*
+ * ECC registration: replaces the loop body of register_ecc (src/registration/registration.c:786-930),
+ * findTransform (src/opencv/ecc/ecc.cpp:556-603) with WARP_MODE_TRANSLATION, 50 iterations, eps
+ * 0.001, on frames resident in HBM.  OpenCV is not pinned by the reference: its published algorithm
+ * is restated (tests/ecc_ref.py is the literal form), so parity is unpinned, as for sg_warp_u16.
+ * Per frame != ref_image, in memory-order coordinates:
+ *   - convertTo(CV_8UC1) SATURATES (min(v, 255), no rescale: the method is meant for 8-bit data held
+ *     in WORDs), GaussianBlur 5x5 sigma 0, reflect-101; gradients (-0.5, 0, 0.5);
+ *   - up to 50 iterations of: warp image and gradients by the current translation (warpAffine's
+ *     1/32-pixel fixed point, bilinear, border 0; nearest for the mask), masked means and norms,
+ *     2x2 Hessian, rho, lambda, the update of (tx, ty); it ends when |rho - last_rho| < 0.001;
+ *   - success when rho > 0: dx = tx, dy = ty; -1 < rho <= 0 is success with dx = dy = 0 (findTransform
+ *     returns (int)rho and the caller's memset zeros stand); rho = -1 or a non-finite rho or update:
+ *     failed, the frame is to be excluded (incl = FALSE) and its shifts are 0;
+ *   - shiftx = -round_to_int(dx), shifty = -round_to_int(dy).
+ * The reference frame gets shifts 0, dx = dy = 0, rho 0, iterations 0, failed 0.  Frames outside
+ * `included` (NULL = all) are neither registered nor written.  The quality register_ecc also stores
+ * (QualityEstimate of the whole layer) is not computed here; see INTEGRATION.md.
+ * Frames are read in place: frame f, row r, column x at d_frames[f * frame_pitch + r * row_pitch + x]
+ * (elements; 0 = tight: row_pitch W, frame_pitch H * row_pitch), e.g. layer `layer` of [C][H][W]
+ * frames: d_frames = frames + layer H W, frame_pitch = C H W, row_pitch = W; never written.
+ * SG_ERR_SIZE with a message: W or H below 8 or above 65536, a plane of 2^31 pixels or more,
+ * nframes < 1, row_pitch < W, frame_pitch below a frame's extent, ref_image outside [0, nframes).
+ * Synchronous; results are the same bits on every run.
+ */
+typedef struct {
+	int *shiftx, *shifty;	/* host [nframes] */
+	float *dx, *dy;		/* host [nframes], may be NULL */
+	double *rho;		/* host [nframes], may be NULL: the last correlation coefficient */
+	int *iterations;	/* host [nframes], may be NULL: loop bodies run */
+	int *failed;		/* host [nframes], may be NULL: 1 = findTransform failed */
+} sg_ecc_out;
+int sg_register_ecc_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_frames, int64_t frame_pitch,
+		int64_t row_pitch, int W, int H, int nframes, int ref_image, const int *included, const sg_ecc_out *out,
+		void *stream);
+/* the same on host frames with the same pitches, uploaded in batches, on device 0 of the context */
+int sg_register_ecc_u16(sg_ctx *ctx, const uint16_t *frames, int64_t frame_pitch, int64_t row_pitch, int W, int H,
+		int nframes, int ref_image, const int *included, const sg_ecc_out *out);
+
+/* the last ECC call on that device: the device time of its per-frame prepare launches, of its
+ * iteration launches (HIP events; the second span includes the host's reads of the unfinished-frame
+ * count between groups of launches) and the number of iteration launches.  Any pointer may be NULL. */
+int sg_register_ecc_last_times(sg_ctx *ctx, int dev_index, double *prepare_ms, double *iterate_ms, int *launches);
+
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
  * (frame_stride 0 = nb_layers*height*width). */

@@ -105,6 +105,11 @@ struct SgDevice {
 	/* star candidates (sg_findstar.hip): histograms / records / masks / row offsets, the scratch
 	 * detection plane, the candidate list and boxes, host frames of sg_findstar */
 	SgBuf fs_work, fs_plane, fs_out, fs_frames, fs_fit;	/* fs_fit: the fit records of sg_findstar_fit* */
+	/* ECC registration (sg_ecc.hip): the template and the chunk's blurred planes, partial moments,
+	 * states and tickets in one block; host frames of sg_register_ecc_u16 */
+	SgBuf ecc_work, ecc_frames;
+	double ecc_prep_ms = 0., ecc_iter_ms = 0.;	/* the last ECC call: device spans of its prepare and iteration launches */
+	int ecc_launches = 0;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };
@@ -158,6 +163,7 @@ struct SgKnobs {
 	int norm_fma = 2;		/* SG_NORM_FMA: normalised histogram stacks load with one fma per sample (1, 2) or, additive with
 					 * scale 1, an integer offset (2) when a device check (k_norm_fma_check) finds that equal to the
 					 * reference's roundings for every u16 value of every frame; 0 = the reference's operations */
+	int ecc_chunk = 0;		/* SG_ECC_CHUNK: frames per chunk of sg_register_ecc_u16* (0 = from the byte budget; tests of the chunk loop) */
 	int reg_rpb = 4;		/* SG_REG_RPB: rows per forward-row workgroup of the half-spectrum path (1 -> 4: 6.46 -> 5.92 ms registration on configs[1], profiles/r03u_ab_reg_rows.log) */
 	void read() {
 		hist_dbg = sg_env_int("SG_HIST_DBG", 0, 1000, 0);
@@ -203,6 +209,7 @@ struct SgKnobs {
 		reg_rpw = sg_env_int("SG_REG_RPW", 1, 64, 8);
 		reg_qfold = sg_env_int("SG_REG_QFOLD", 0, 63, 12) / 3 * 3;
 		norm_fma = sg_env_int("SG_NORM_FMA", 0, 2, 2);
+		ecc_chunk = sg_env_int("SG_ECC_CHUNK", 1, 65535, 0);
 	}
 };
 

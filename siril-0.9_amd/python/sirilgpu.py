@@ -125,6 +125,13 @@ class SeqInfo(ctypes.Structure):
                 ("ser_color_id", ctypes.c_int), ("frame_bytes", ctypes.c_int64)]
 
 
+class EccOut(ctypes.Structure):
+    """sg_ecc_out: per-frame host arrays"""
+    _fields_ = [("shiftx", ctypes.c_void_p), ("shifty", ctypes.c_void_p), ("dx", ctypes.c_void_p),
+                ("dy", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("iterations", ctypes.c_void_p),
+                ("failed", ctypes.c_void_p)]
+
+
 # every symbol include/sirilgpu.h and include/sirilgpu_io.h declare
 EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_u16_device",
            "sg_stack_u16_device_async", "sg_stack_collect", "sg_stack_wait_tail", "sg_device_count",
@@ -137,7 +144,8 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_seqfile_get_registration", "sg_seqfile_set_registration", "sg_seqfile_write",
            "sg_prepro_create", "sg_prepro_free", "sg_prepro_get_info", "sg_prepro_frames_device",
            "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar",
-           "sg_findstar_fit_device", "sg_findstar_fit"]
+           "sg_findstar_fit_device", "sg_findstar_fit", "sg_register_ecc_u16_device", "sg_register_ecc_u16",
+           "sg_register_ecc_last_times"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -264,6 +272,15 @@ def load():
     lib.sg_findstar_fit_device.restype = ctypes.c_int
     lib.sg_findstar_fit.argtypes = [P, ctypes.POINTER(StarfitDesc), P, ctypes.c_int, ctypes.POINTER(FindstarFrame), P, P, P]
     lib.sg_findstar_fit.restype = ctypes.c_int
+    lib.sg_register_ecc_u16_device.argtypes = [P, ctypes.c_int, P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.POINTER(EccOut), P]
+    lib.sg_register_ecc_u16_device.restype = ctypes.c_int
+    lib.sg_register_ecc_u16.argtypes = [P, P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, P, ctypes.POINTER(EccOut)]
+    lib.sg_register_ecc_u16.restype = ctypes.c_int
+    lib.sg_register_ecc_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+    lib.sg_register_ecc_last_times.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -718,6 +735,49 @@ class Context:
         rc = fn(self.ctx, dev_index, P(d_sel), nframes, S, ref_image, *args, P(stream) if stream else None)
         self.check(rc, "sg_register_dft_u16_device" + ("_raw" if raw_quality else ""))
         return sx, sy, q
+
+    @staticmethod
+    def _ecc_arrays(nframes):
+        res = {"shiftx": np.zeros(nframes, dtype=np.int32), "shifty": np.zeros(nframes, dtype=np.int32),
+               "dx": np.zeros(nframes, dtype=np.float32), "dy": np.zeros(nframes, dtype=np.float32),
+               "rho": np.zeros(nframes, dtype=np.float64), "iterations": np.zeros(nframes, dtype=np.int32),
+               "failed": np.zeros(nframes, dtype=np.int32)}
+        out = EccOut(*[res[k].ctypes.data for k, _ in EccOut._fields_])
+        return res, out
+
+    def register_ecc_device(self, d_frames, nframes, H, W, ref_image=0, included=None, frame_pitch=0, row_pitch=0,
+                            stream=None, dev_index=0):
+        """register_ecc's per-frame work on resident frames read in place (sg_register_ecc_u16_device): frame f,
+        row r at d_frames + f * frame_pitch + r * row_pitch elements (0 = tight).  Returns (rc, dict of the
+        per-frame arrays shiftx, shifty, dx, dy, rho, iterations, failed); frames outside `included` keep 0."""
+        inc = None if included is None else np.ascontiguousarray(included, dtype=np.int32)
+        res, out = self._ecc_arrays(nframes)
+        P = ctypes.c_void_p
+        rc = self.lib.sg_register_ecc_u16_device(self.ctx, dev_index, P(d_frames), frame_pitch, row_pitch, W, H, nframes,
+                                                 ref_image, inc.ctypes.data_as(P) if inc is not None else None,
+                                                 ctypes.byref(out), P(stream) if stream else None)
+        return rc, res
+
+    def register_ecc_last_times(self, dev_index=0):
+        """(prepare ms, iterate ms, iteration launches) of the last ECC call on that device"""
+        a, b, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        self.check(self.lib.sg_register_ecc_last_times(self.ctx, dev_index, ctypes.byref(a), ctypes.byref(b),
+                                                       ctypes.byref(n)), "sg_register_ecc_last_times")
+        return a.value, b.value, n.value
+
+    def register_ecc(self, frames, ref_image=0, included=None, layer=0):
+        """the same on host frames [N][H][W] or [N][C][H][W] u16, layer `layer` (sg_register_ecc_u16)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.ndim == 3:
+            frames = frames[:, None]
+        N, C, H, W = frames.shape
+        inc = None if included is None else np.ascontiguousarray(included, dtype=np.int32)
+        res, out = self._ecc_arrays(N)
+        P = ctypes.c_void_p
+        base = frames.ctypes.data + layer * H * W * 2
+        rc = self.lib.sg_register_ecc_u16(self.ctx, P(base), C * H * W, W, W, H, N, ref_image,
+                                          inc.ctypes.data_as(P) if inc is not None else None, ctypes.byref(out))
+        return rc, res
 
     def prepro_frames_device(self, prepro, d_frames, nframes, frame_stride=0, want_k=True, stream=None, dev_index=0):
         """seqpreprocess's loop body on resident frames, in place (sg_prepro_frames_device); returns
