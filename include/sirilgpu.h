@@ -552,6 +552,68 @@ int sg_register_ecc_u16(sg_ctx *ctx, const uint16_t *frames, int64_t frame_pitch
  * count between groups of launches) and the number of iteration launches.  Any pointer may be NULL. */
 int sg_register_ecc_last_times(sg_ctx *ctx, int dev_index, double *prepare_ms, double *iterate_ms, int *launches);
 
+/*
+ * Automatic cosmetic correction: seqfind_cosme / seqfind_cosme_cfa / find_cosme and the GUI's
+ * "Cosmetic Correction" (apply_cosmetic_to_sequence -> cosmetic_image_hook -> autoDetect,
+ * src/algos/cosmetic_correction.c:296-435; process_findcosme, src/core/command.c:1294-1318) on
+ * frames resident in HBM, in place, bit for bit.  Per frame and per layer 0 .. nb_layers - 1 in
+ * turn, on the plane in memory order (y outer, x inner):
+ *   1. statistics(fit, layer, NULL, STATS_BASIC | STATS_AVGDEV, STATS_ZERO_NULLCHECK): ngood = the
+ *      non-zero pixels; bkg = the histogram median over bins 1 .. 65534 (the first bin whose running
+ *      count exceeds ngood * 0.5, else 0; 65535 is not binned but counts in ngood); avgDev = the sum
+ *      of |v - bkg| over the non-zero pixels (an exact integer) divided by ngood in double.
+ *      ngood == 0: autoDetect returns 1, the frame fails at this layer (status = 1, failed_layer),
+ *      the earlier layers stay corrected, this and the later ones are untouched.  A failed frame
+ *      does not fail the call.
+ *   2. the scan: a = getAverage3x3, m = getMedian5x5 (step 2, radius 2 / 4 with is_cfa; the
+ *      start = 24 - n - 1 quirk: the median of one zero and the n - 1 smallest in-frame neighbours),
+ *      both of the buffer as it stands when the scan reaches the pixel, so a pixel sees the
+ *      corrections of the pixels before it.  Hot, unless sig[1] == -1:
+ *      a < bkg + avgDev / 2 && pixel > bkg + avgDev && pixel > m + sig[1] * avgDev: ihot++,
+ *      buf = a * amount + pixel * (1 - amount), in double as written, truncated to WORD.  Cold,
+ *      unless sig[0] == -1: pixel + avgDev * sig[0] < bkg && pixel + avgDev * sig[0] < m: icold++,
+ *      buf = m * amount + pixel * (1 - amount).
+ *   3. icold and ihot are summed over the layers of a frame.
+ * The result is the serial scan's for every input and the same bits on every run.  A pixel without
+ * any neighbour at distance `step` (only CFA planes of at most 3 x 3 have one) takes a = 0 where
+ * the reference converts a NaN.
+ * Refused before any device work: SG_ERR_SIZE for a dimension <= 0, a plane of 2^31 pixels or
+ * more, nb_layers outside [1, 3], nframes < 1, a frame_stride below one frame, a plane in which no
+ * pixel has a neighbour (width <= step and height <= step: the reference divides 0 by 0);
+ * SG_ERR_GENERIC for a sig that is NaN or negative and not exactly -1, an amount outside [0, 1].
+ * amount is a parameter: process_findcosme leaves it uninitialised, the GUI sets it.
+ * Left to the caller: writing the cc_ sequence, the list-driven `cosme` command, sharding over
+ * devices; see INTEGRATION.md.
+ */
+typedef struct {
+	int width, height, nb_layers;
+	double sig[2];		/* {cold, hot}; -1 switches the test off */
+	double amount;
+	int is_cfa;
+} sg_cosme_desc;
+
+typedef struct {
+	int status;		/* 0: corrected; 1: a layer without a non-zero pixel */
+	int failed_layer;	/* that layer, else -1 */
+	int64_t icold, ihot;
+	double bkg[3], avg_dev[3];	/* per layer reached (0 for the others) */
+} sg_cosme_frame;
+
+/* frames: frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
+ * (frame_stride 0 = C*H*W), corrected in place; out[nframes].  nframes = 1 is find_cosme.
+ * Synchronous. */
+int sg_cosme_autodetect_device(sg_ctx *ctx, int dev_index, const sg_cosme_desc *desc, uint16_t *d_frames,
+		int nframes, int64_t frame_stride, void *stream, sg_cosme_frame *out);
+/* the same on host frames [nframes][C][H][W], in place, uploaded in batches, on device 0 of the
+ * context */
+int sg_cosme_autodetect(sg_ctx *ctx, const sg_cosme_desc *desc, uint16_t *frames, int nframes,
+		sg_cosme_frame *out);
+/* the last call on that device: device time (HIP events) of its statistics, main pass and
+ * dependence resolution (with the host's looks at the active count), the rounds launched, and the
+ * pixels re-examined by them.  Any pointer may be NULL. */
+int sg_cosme_last_times(sg_ctx *ctx, int dev_index, double *stat_ms, double *main_ms, double *resolve_ms,
+		int *rounds, int64_t *reexamined);
+
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
  * (frame_stride 0 = nb_layers*height*width). */

@@ -110,6 +110,12 @@ struct SgDevice {
 	SgBuf ecc_work, ecc_frames;
 	double ecc_prep_ms = 0., ecc_iter_ms = 0.;	/* the last ECC call: device spans of its prepare and iteration launches */
 	int ecc_launches = 0;
+	/* automatic cosmetic correction (sg_cosme.hip): one chunk's scratch (sg_cosme_plan.hpp); host
+	 * frames of sg_cosme_autodetect; the last call's device spans */
+	SgBuf cosme_work, cosme_frames;
+	double cosme_stat_ms = 0., cosme_main_ms = 0., cosme_resolve_ms = 0.;
+	int cosme_rounds = 0;
+	long long cosme_reexamined = 0;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };
@@ -164,6 +170,8 @@ struct SgKnobs {
 					 * scale 1, an integer offset (2) when a device check (k_norm_fma_check) finds that equal to the
 					 * reference's roundings for every u16 value of every frame; 0 = the reference's operations */
 	int ecc_chunk = 0;		/* SG_ECC_CHUNK: frames per chunk of sg_register_ecc_u16* (0 = from the byte budget; tests of the chunk loop) */
+	int cosme_chunk = 0;		/* SG_COSME_CHUNK: frames per chunk of sg_cosme_autodetect* (0 = from the byte budget; tests of the chunk loop) */
+	int cosme_list = 0;		/* SG_COSME_LIST: capacity of a round's pixel list (0 = an eighth of the chunk's pixels, at least 65536; tests of the overflow) */
 	int reg_rpb = 4;		/* SG_REG_RPB: rows per forward-row workgroup of the half-spectrum path (1 -> 4: 6.46 -> 5.92 ms registration on configs[1], profiles/r03u_ab_reg_rows.log) */
 	void read() {
 		hist_dbg = sg_env_int("SG_HIST_DBG", 0, 1000, 0);
@@ -199,6 +207,8 @@ struct SgKnobs {
 			reg_cw32 &= reg_cw32 - 1;
 		reg_colocc = sg_env_int("SG_REG_COLOCC", 0, 1, 1);
 		reg_rpb = sg_env_int("SG_REG_RPB", 1, 64, 4);
+		cosme_chunk = sg_env_int("SG_COSME_CHUNK", 1, 65535, 0);
+		cosme_list = sg_env_int("SG_COSME_LIST", 1, 1 << 30, 0);
 		reg_refconc = sg_env_int("SG_REG_REFCONC", 0, 1, 1);
 		reg_specp = sg_env_int("SG_REG_SPECP", 0, 1, 1);
 		reg_wcolw = sg_env_int("SG_REG_WCOLW", 4, 8, 8) == 8 ? 8 : 4;

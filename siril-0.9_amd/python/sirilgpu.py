@@ -132,6 +132,17 @@ class EccOut(ctypes.Structure):
                 ("failed", ctypes.c_void_p)]
 
 
+class CosmeDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("nb_layers", ctypes.c_int),
+                ("sig", ctypes.c_double * 2), ("amount", ctypes.c_double), ("is_cfa", ctypes.c_int)]
+
+
+class CosmeFrame(ctypes.Structure):
+    """sg_cosme_frame: one frame's outcome of the automatic cosmetic correction"""
+    _fields_ = [("status", ctypes.c_int), ("failed_layer", ctypes.c_int), ("icold", ctypes.c_int64),
+                ("ihot", ctypes.c_int64), ("bkg", ctypes.c_double * 3), ("avg_dev", ctypes.c_double * 3)]
+
+
 # every symbol include/sirilgpu.h and include/sirilgpu_io.h declare
 EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_u16_device",
            "sg_stack_u16_device_async", "sg_stack_collect", "sg_stack_wait_tail", "sg_device_count",
@@ -145,7 +156,7 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_prepro_create", "sg_prepro_free", "sg_prepro_get_info", "sg_prepro_frames_device",
            "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar",
            "sg_findstar_fit_device", "sg_findstar_fit", "sg_register_ecc_u16_device", "sg_register_ecc_u16",
-           "sg_register_ecc_last_times"]
+           "sg_register_ecc_last_times", "sg_cosme_autodetect_device", "sg_cosme_autodetect", "sg_cosme_last_times"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -281,6 +292,15 @@ def load():
     lib.sg_register_ecc_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     lib.sg_register_ecc_last_times.restype = ctypes.c_int
+    lib.sg_cosme_autodetect_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(CosmeDesc), P, ctypes.c_int, ctypes.c_int64,
+                                               P, ctypes.POINTER(CosmeFrame)]
+    lib.sg_cosme_autodetect_device.restype = ctypes.c_int
+    lib.sg_cosme_autodetect.argtypes = [P, ctypes.POINTER(CosmeDesc), P, ctypes.c_int, ctypes.POINTER(CosmeFrame)]
+    lib.sg_cosme_autodetect.restype = ctypes.c_int
+    lib.sg_cosme_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_int64)]
+    lib.sg_cosme_last_times.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -516,6 +536,15 @@ def make_starfit_desc(W, H, C, layer, radius, sigma, area=None, max_candidates=2
     d.roundness, d.norm = roundness, norm
     d.fwhm_scale_x, d.fwhm_scale_y = fwhm_scales
     d.max_stars, d.want_candidates = max_stars, int(bool(want_candidates))
+    return d
+
+
+def make_cosme_desc(W, H, C, sig=(3.0, 3.0), amount=1.0, is_cfa=False):
+    """sg_cosme_desc: sig = (cold, hot), -1 switches a test off"""
+    d = CosmeDesc()
+    d.width, d.height, d.nb_layers = W, H, C
+    d.sig[0], d.sig[1] = float(sig[0]), float(sig[1])
+    d.amount, d.is_cfa = float(amount), int(bool(is_cfa))
     return d
 
 
@@ -778,6 +807,35 @@ class Context:
         rc = self.lib.sg_register_ecc_u16(self.ctx, P(base), C * H * W, W, W, H, N, ref_image,
                                           inc.ctypes.data_as(P) if inc is not None else None, ctypes.byref(out))
         return rc, res
+
+    def cosme_autodetect_device(self, d_frames, nframes, C, H, W, sig=(3.0, 3.0), amount=1.0, is_cfa=False,
+                                frame_stride=0, stream=None, dev_index=0):
+        """seqfind_cosme's per-frame work (autoDetect on every layer) on resident frames, in place
+        (sg_cosme_autodetect_device); returns (rc, list of CosmeFrame)"""
+        d = make_cosme_desc(W, H, C, sig, amount, is_cfa)
+        rec = (CosmeFrame * max(nframes, 1))()
+        rc = self.lib.sg_cosme_autodetect_device(self.ctx, dev_index, ctypes.byref(d), ctypes.c_void_p(d_frames), nframes,
+                                                 frame_stride, ctypes.c_void_p(stream) if stream else None, rec)
+        return rc, list(rec)[:max(nframes, 0)]
+
+    def cosme_autodetect(self, frames, sig=(3.0, 3.0), amount=1.0, is_cfa=False):
+        """the same on host frames [N][C][H][W] u16, corrected in place (sg_cosme_autodetect); returns
+        (rc, list of CosmeFrame)"""
+        assert frames.dtype == np.uint16 and frames.flags.c_contiguous and frames.flags.writeable and frames.ndim == 4
+        N, C, H, W = frames.shape
+        d = make_cosme_desc(W, H, C, sig, amount, is_cfa)
+        rec = (CosmeFrame * max(N, 1))()
+        rc = self.lib.sg_cosme_autodetect(self.ctx, ctypes.byref(d), frames.ctypes.data_as(ctypes.c_void_p), N, rec)
+        return rc, list(rec)[:N]
+
+    def cosme_last_times(self, dev_index=0):
+        """(statistics ms, main pass ms, dependence resolution ms, rounds, pixels re-examined) of the last
+        cosmetic correction call on that device"""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        n, m = ctypes.c_int(), ctypes.c_int64()
+        self.check(self.lib.sg_cosme_last_times(self.ctx, dev_index, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                                ctypes.byref(n), ctypes.byref(m)), "sg_cosme_last_times")
+        return a.value, b.value, c.value, n.value, m.value
 
     def prepro_frames_device(self, prepro, d_frames, nframes, frame_stride=0, want_k=True, stream=None, dev_index=0):
         """seqpreprocess's loop body on resident frames, in place (sg_prepro_frames_device); returns
