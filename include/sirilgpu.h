@@ -525,7 +525,7 @@ int sg_findstar_fit(sg_ctx *ctx, const sg_starfit_desc *desc, const uint16_t *fr
  *   - shiftx = -round_to_int(dx), shifty = -round_to_int(dy).
  * The reference frame gets shifts 0, dx = dy = 0, rho 0, iterations 0, failed 0.  Frames outside
  * `included` (NULL = all) are neither registered nor written.  The quality register_ecc also stores
- * (QualityEstimate of the whole layer) is not computed here; see INTEGRATION.md.
+ * (QualityEstimate of the whole layer) is sg_quality_u16_device's, below; see INTEGRATION.md.
  * Frames are read in place: frame f, row r, column x at d_frames[f * frame_pitch + r * row_pitch + x]
  * (elements; 0 = tight: row_pitch W, frame_pitch H * row_pitch), e.g. layer `layer` of [C][H][W]
  * frames: d_frames = frames + layer H W, frame_pitch = C H W, row_pitch = W; never written.
@@ -613,6 +613,79 @@ int sg_cosme_autodetect(sg_ctx *ctx, const sg_cosme_desc *desc, uint16_t *frames
  * pixels re-examined by them.  Any pointer may be NULL. */
 int sg_cosme_last_times(sg_ctx *ctx, int dev_index, double *stat_ms, double *main_ms, double *resolve_ms,
 		int *rounds, int64_t *reexamined);
+
+/*
+ * Quality of whole layers: QualityEstimate(fit, layer, QUALTYPE_NORMAL) (src/algos/quality.c:46-218),
+ * the number register_ecc stores per frame (src/registration/registration.c:833, 892), of W x H planes
+ * resident in HBM, bit for bit with oracle/or_registration.c: or_quality_estimate and the same bits
+ * on every run.  Only subsample 3 contributes (quality.c:192-194 weights the others by an integer
+ * quotient that is 0).  On the plane in memory order, as fit->pdata[layer] is:
+ *   1. xs = (W - 1) / 3, ys = (H - 1) / 3; with xs < 2 || ys < 2 the result is 0.0, nothing is launched;
+ *   2. sample (j, i) = the integer average of rows 3j .. 3j + 2, columns 3i .. 3i + 2;
+ *   3. max = the largest sample of rows 1 .. ys - 2 with 0 < v < 65530;
+ *   4. max > 0: v = (unsigned)((double)v * (60000.0 / max)) clamped at 65535, in fp64 as written;
+ *   5. the 3 x 3 integer box / 9, the border ring 0;
+ *   6. xb = (int)(xs * 0.1) + 1, yb = (int)(ys * 0.1) + 1: a pixel inside the margins whose smoothed
+ *      value is >= 10240 flags its 3 x 3 neighbourhood; flagged pixels inside the margins add
+ *      d1^2 + d2^2 (differences to the right and to the next row) and count;
+ *   7. sqrt(val / pixels / 10), NaN when nothing passed the threshold.
+ * The sums are exact integers, converted once: equality with the reference's double accumulation
+ * holds while val < 2^53 (the limit the DFT path's quality has too).
+ * Frames are read in place: frame f, row r, column x at d_frames[f * frame_pitch + r * row_pitch + x]
+ * (elements; 0 = tight: row_pitch W, frame_pitch H * row_pitch), e.g. layer `layer` of [C][H][W]
+ * frames: d_frames = frames + layer H W, frame_pitch = C H W, row_pitch = W; never written.  Any
+ * base alignment, odd widths and odd pitches are taken.
+ * quality_raw: host [nframes]; frames outside `included` (NULL = all) are not written.
+ * A frame small enough for one workgroup's LDS (up to 40952 samples, e.g. 640 x 480) is estimated by
+ * one workgroup without scratch; larger planes go through a u16 sample plane in HBM, in chunks of
+ * frames.  Both routes give the same bits.
+ * SG_ERR_SIZE with a message, before any device work: W or H <= 0, a plane of 2^31 pixels or more,
+ * nframes < 1, row_pitch < W, frame_pitch below a frame's extent.  Synchronous.
+ * Left to the caller: sharding a sequence over devices.  The DFT path (sg_register_dft_*) keeps its
+ * own quality of the square selection.
+ */
+int sg_quality_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_frames, int64_t frame_pitch, int64_t row_pitch,
+		int W, int H, int nframes, const int *included, double *quality_raw, void *stream);
+/* the same on host frames with the same pitches, uploaded in batches, on device 0 of the context */
+int sg_quality_u16(sg_ctx *ctx, const uint16_t *frames, int64_t frame_pitch, int64_t row_pitch, int W, int H,
+		int nframes, const int *included, double *quality_raw);
+/* the last quality call on that device: the device time of its launches (HIP events), the route
+ * taken (0: none, xs < 2 || ys < 2; 1: resident, one workgroup per frame; 2: tiled) and the number
+ * of kernel launches.  Any pointer may be NULL. */
+int sg_quality_last_times(sg_ctx *ctx, int dev_index, double *ms, int *route, int *launches);
+
+/*
+ * The bookkeeping of register_ecc around the raw values (registration.c:838, 899-905) and
+ * normalizeQualityData (:163-176).  No context is needed.
+ *   q_min = q_max = quality_raw[ref_image], q_index = ref_image; then for frame = 0 .. nframes - 1,
+ *   frame != ref_image, measured[frame] (NULL = all), in index order:
+ *       if (qual > q_max) { q_max = qual; q_index = frame; }   q_min = q_min < qual ? q_min : qual;
+ *   so a NaN behaves as it does there (it never raises q_max; it replaces q_min, and the next
+ *   measured value replaces it again).  The serial order is the contract.
+ *   quality[frame] = quality_raw[frame] for the reference and the measured frames, 0 for the others
+ *   (ECC leaves out the frames whose findTransform failed; their regdata stays zeroed); then every
+ *   frame with normalized[frame] (NULL = all) becomes (quality - q_min) / (q_max - q_min), by a
+ *   subtraction and a division as written (q_max == q_min divides by 0 as the reference does).
+ * quality may be quality_raw.  q_min, q_max, q_index, msg may be NULL.  SG_ERR_SIZE: nframes < 1 or
+ * ref_image outside [0, nframes); SG_ERR_GENERIC: a missing array; the reason goes to msg.
+ */
+int sg_quality_normalize(int nframes, int ref_image, const double *quality_raw, const int *measured,
+		const int *normalized, double *quality, double *q_min, double *q_max, int *q_index, char *msg, int msg_len);
+
+/*
+ * "Stack the best percent % of the frames": compute_highest_accepted_quality
+ * (src/stacking/stacking.c:2283-2310), stack_filter_quality (:2204-2213) and
+ * fill_list_of_unfiltered_images (:2230-2241).  quality[i] is the value of every frame, included or
+ * not (included NULL = all).  If an included frame has a negative quality: *threshold = 0.0,
+ * *nselected = 0, SG_OK (the reference logs and returns 0.0).  Otherwise the values are sorted
+ * ascending, *threshold = val[(int)((100.0 - percent) * (double)nframes / 100.0)], and selected[]
+ * (host [nframes], may be NULL for the count alone) receives, in index order, the frames with
+ * included && quality > 0.0 && quality >= threshold.  SG_ERR_GENERIC with the reason in msg where the
+ * reference reads outside its array (an index >= nframes or < 0, e.g. percent 0) and where a value is
+ * NaN (its sort is then undefined).  No context is needed.
+ */
+int sg_quality_select(int nframes, const double *quality, const int *included, double percent, double *threshold,
+		int *selected, int *nselected, char *msg, int msg_len);
 
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]

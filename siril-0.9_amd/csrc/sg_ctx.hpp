@@ -116,6 +116,11 @@ struct SgDevice {
 	double cosme_stat_ms = 0., cosme_main_ms = 0., cosme_resolve_ms = 0.;
 	int cosme_rounds = 0;
 	long long cosme_reexamined = 0;
+	/* quality estimate of whole layers (sg_quality.hip): one chunk's scratch (sg_quality_plan.hpp);
+	 * host frames of sg_quality_u16; the last call's device span, route and launches */
+	SgBuf quality_work, quality_frames;
+	double quality_ms = 0.;
+	int quality_route = 0, quality_launches = 0;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };
@@ -172,6 +177,9 @@ struct SgKnobs {
 	int ecc_chunk = 0;		/* SG_ECC_CHUNK: frames per chunk of sg_register_ecc_u16* (0 = from the byte budget; tests of the chunk loop) */
 	int cosme_chunk = 0;		/* SG_COSME_CHUNK: frames per chunk of sg_cosme_autodetect* (0 = from the byte budget; tests of the chunk loop) */
 	int cosme_list = 0;		/* SG_COSME_LIST: capacity of a round's pixel list (0 = an eighth of the chunk's pixels, at least 65536; tests of the overflow) */
+	int quality_route = 0;		/* SG_QUALITY_ROUTE: sg_quality_u16*: 0 = the plan's choice, 1 = the resident route where a frame fits, 2 = the tiled route */
+	int quality_chunk = 0;		/* SG_QUALITY_CHUNK: frames per chunk of sg_quality_u16* (0 = from the byte budget; tests of the chunk loop) */
+	int quality_lds = 0;		/* SG_QUALITY_LDS: the resident route's LDS budget in bytes (0 = 160 KiB; tests move the boundary down to a small frame) */
 	int reg_rpb = 4;		/* SG_REG_RPB: rows per forward-row workgroup of the half-spectrum path (1 -> 4: 6.46 -> 5.92 ms registration on configs[1], profiles/r03u_ab_reg_rows.log) */
 	void read() {
 		hist_dbg = sg_env_int("SG_HIST_DBG", 0, 1000, 0);
@@ -209,6 +217,9 @@ struct SgKnobs {
 		reg_rpb = sg_env_int("SG_REG_RPB", 1, 64, 4);
 		cosme_chunk = sg_env_int("SG_COSME_CHUNK", 1, 65535, 0);
 		cosme_list = sg_env_int("SG_COSME_LIST", 1, 1 << 30, 0);
+		quality_route = sg_env_int("SG_QUALITY_ROUTE", 0, 2, 0);
+		quality_chunk = sg_env_int("SG_QUALITY_CHUNK", 1, 65535, 0);
+		quality_lds = sg_env_int("SG_QUALITY_LDS", 64, 160 * 1024, 0);
 		reg_refconc = sg_env_int("SG_REG_REFCONC", 0, 1, 1);
 		reg_specp = sg_env_int("SG_REG_SPECP", 0, 1, 1);
 		reg_wcolw = sg_env_int("SG_REG_WCOLW", 4, 8, 8) == 8 ? 8 : 4;

@@ -156,7 +156,8 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_prepro_create", "sg_prepro_free", "sg_prepro_get_info", "sg_prepro_frames_device",
            "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar",
            "sg_findstar_fit_device", "sg_findstar_fit", "sg_register_ecc_u16_device", "sg_register_ecc_u16",
-           "sg_register_ecc_last_times", "sg_cosme_autodetect_device", "sg_cosme_autodetect", "sg_cosme_last_times"]
+           "sg_register_ecc_last_times", "sg_cosme_autodetect_device", "sg_cosme_autodetect", "sg_cosme_last_times",
+           "sg_quality_u16_device", "sg_quality_u16", "sg_quality_last_times", "sg_quality_normalize", "sg_quality_select"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -301,6 +302,21 @@ def load():
                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
                                         ctypes.POINTER(ctypes.c_int64)]
     lib.sg_cosme_last_times.restype = ctypes.c_int
+    lib.sg_quality_u16_device.argtypes = [P, ctypes.c_int, P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, P, P, P]
+    lib.sg_quality_u16_device.restype = ctypes.c_int
+    lib.sg_quality_u16.argtypes = [P, P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]
+    lib.sg_quality_u16.restype = ctypes.c_int
+    lib.sg_quality_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int)]
+    lib.sg_quality_last_times.restype = ctypes.c_int
+    lib.sg_quality_normalize.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P, ctypes.POINTER(ctypes.c_double),
+                                         ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int), ctypes.c_char_p,
+                                         ctypes.c_int]
+    lib.sg_quality_normalize.restype = ctypes.c_int
+    lib.sg_quality_select.argtypes = [ctypes.c_int, P, P, ctypes.c_double, ctypes.POINTER(ctypes.c_double), P,
+                                      ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, ctypes.c_int]
+    lib.sg_quality_select.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -837,6 +853,39 @@ class Context:
                                                 ctypes.byref(n), ctypes.byref(m)), "sg_cosme_last_times")
         return a.value, b.value, c.value, n.value, m.value
 
+    def quality_device(self, d_frames, nframes, H, W, included=None, frame_pitch=0, row_pitch=0, stream=None, dev_index=0,
+                       fill=0.0):
+        """QualityEstimate of W x H planes resident in HBM, read in place (sg_quality_u16_device): frame f, row r at
+        d_frames + f * frame_pitch + r * row_pitch elements (0 = tight).  Returns (rc, quality_raw[nframes]);
+        frames outside `included` keep `fill`."""
+        inc = None if included is None else np.ascontiguousarray(included, dtype=np.int32)
+        q = np.full(max(nframes, 0), fill, dtype=np.float64)
+        P = ctypes.c_void_p
+        rc = self.lib.sg_quality_u16_device(self.ctx, dev_index, P(d_frames), frame_pitch, row_pitch, W, H, nframes,
+                                            inc.ctypes.data_as(P) if inc is not None else None,
+                                            q.ctypes.data_as(P) if q.size else None, P(stream) if stream else None)
+        return rc, q
+
+    def quality(self, frames, included=None, layer=0, fill=0.0):
+        """the same on host frames [N][H][W] or [N][C][H][W] u16, layer `layer` (sg_quality_u16)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.ndim == 3:
+            frames = frames[:, None]
+        N, C, H, W = frames.shape
+        inc = None if included is None else np.ascontiguousarray(included, dtype=np.int32)
+        q = np.full(N, fill, dtype=np.float64)
+        P = ctypes.c_void_p
+        rc = self.lib.sg_quality_u16(self.ctx, P(frames.ctypes.data + layer * H * W * 2), C * H * W, W, W, H, N,
+                                     inc.ctypes.data_as(P) if inc is not None else None, q.ctypes.data_as(P))
+        return rc, q
+
+    def quality_last_times(self, dev_index=0):
+        """(device ms, route: 0 none / 1 resident / 2 tiled, kernel launches) of the last quality call on that device"""
+        a, r, n = ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
+        self.check(self.lib.sg_quality_last_times(self.ctx, dev_index, ctypes.byref(a), ctypes.byref(r), ctypes.byref(n)),
+                   "sg_quality_last_times")
+        return a.value, r.value, n.value
+
     def prepro_frames_device(self, prepro, d_frames, nframes, frame_stride=0, want_k=True, stream=None, dev_index=0):
         """seqpreprocess's loop body on resident frames, in place (sg_prepro_frames_device); returns
         (rc, dark_k[nframes] or None)"""
@@ -998,3 +1047,45 @@ def compute_normalization(mode, location, scale, ref_image=0):
     if rc != SG_OK:
         raise RuntimeError(f"sg_compute_normalization failed ({rc})")
     return off, mul, so
+
+
+def _mask(a, n):
+    return None if a is None else np.ascontiguousarray(np.asarray(a).astype(bool), dtype=np.int32).reshape(n)
+
+
+def normalize_quality(quality_raw, ref_image=0, measured=None, normalized=None):
+    """register_ecc's q_min / q_max / q_index bookkeeping and normalizeQualityData through the C ABI
+    (sg_quality_normalize): returns (quality, q_min, q_max, q_index)"""
+    lib = load()
+    raw = np.ascontiguousarray(quality_raw, dtype=np.float64)
+    n = raw.size
+    mea, nor = _mask(measured, n), _mask(normalized, n)
+    q = np.zeros(n, dtype=np.float64)
+    lo, hi, idx = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    msg = ctypes.create_string_buffer(256)
+    P = ctypes.c_void_p
+    rc = lib.sg_quality_normalize(n, ref_image, raw.ctypes.data_as(P), mea.ctypes.data_as(P) if mea is not None else None,
+                                  nor.ctypes.data_as(P) if nor is not None else None, q.ctypes.data_as(P),
+                                  ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(idx), msg, len(msg))
+    if rc != SG_OK:
+        raise ValueError(f"sg_quality_normalize failed ({rc}): {msg.value.decode()}")
+    return q, lo.value, hi.value, idx.value
+
+
+def select_by_quality(quality, percent, included=None):
+    """the "best percent % of the frames" filter through the C ABI (sg_quality_select): returns
+    (threshold, indices of the selected frames); raises ValueError where the reference reads outside its
+    array or sorts a NaN"""
+    lib = load()
+    q = np.ascontiguousarray(quality, dtype=np.float64)
+    n = q.size
+    inc = _mask(included, n)
+    sel = np.zeros(max(n, 1), dtype=np.int32)
+    thr, cnt = ctypes.c_double(), ctypes.c_int()
+    msg = ctypes.create_string_buffer(256)
+    P = ctypes.c_void_p
+    rc = lib.sg_quality_select(n, q.ctypes.data_as(P), inc.ctypes.data_as(P) if inc is not None else None, float(percent),
+                               ctypes.byref(thr), sel.ctypes.data_as(P), ctypes.byref(cnt), msg, len(msg))
+    if rc != SG_OK:
+        raise ValueError(f"sg_quality_select failed ({rc}): {msg.value.decode()}")
+    return thr.value, sel[:cnt.value].copy()
