@@ -346,14 +346,14 @@ static int sgc_run(sg_ctx *ctx, int dev_index, const SgCosmePlan &pl, uint16_t *
 		sg_cosme_frame *out) {
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	HIPCHK(ensure(dv.cosme_work, pl.total_bytes + 64));
 	HIPCHK(hipFuncSetAttribute((const void *)k_cosme_hist, hipFuncAttributeMaxDynamicSharedMemorySize,
 			SGC_BINS / 2 * sizeof(uint32_t)));
 	char *wk = (char *)dv.cosme_work.p;
 	/* cleared per chunk: the four bit planes, the histograms, the counters (contiguous) */
 	const size_t o_planes = 0, o_hist = o_planes + 4 * pl.plane_bytes, o_count = o_hist + pl.hist_bytes;
-	const size_t o_cnt = o_count + sgc_up16((size_t)pl.chunk * 2 * sizeof(uint64_t));
+	const size_t o_cnt = o_count + sg_up16((size_t)pl.chunk * 2 * sizeof(uint64_t));
 	const size_t o_clear_end = o_count + pl.count_bytes;
 	const size_t o_rules = o_clear_end, o_list = o_rules + pl.rule_bytes, o_state = o_list + 2 * pl.list_bytes;
 	SgCosmeParams p;
@@ -470,7 +470,7 @@ static int sgc_check(sg_ctx *ctx, SgCosmePlan &pl, const sg_cosme_desc *desc, co
 
 extern "C" int sg_cosme_autodetect_device(sg_ctx *ctx, int dev_index, const sg_cosme_desc *desc, uint16_t *d_frames,
 		int nframes, int64_t frame_stride, void *stream, sg_cosme_frame *out) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	SgCosmePlan pl;
 	const int rc = sgc_check(ctx, pl, desc, d_frames, nframes, frame_stride, out);
@@ -479,7 +479,7 @@ extern "C" int sg_cosme_autodetect_device(sg_ctx *ctx, int dev_index, const sg_c
 	return sgc_run(ctx, dev_index, pl, d_frames, stream, out);
 }
 
-/* host frames [nframes][C][H][W]: uploaded, corrected and downloaded in batches of at most 512 MB;
+/* host frames [nframes][C][H][W]: uploaded, corrected and downloaded in batches of at most 512 MiB;
  * frames are independent, so this equals the device entry */
 extern "C" int sg_cosme_autodetect(sg_ctx *ctx, const sg_cosme_desc *desc, uint16_t *frames, int nframes,
 		sg_cosme_frame *out) {
@@ -489,34 +489,27 @@ extern "C" int sg_cosme_autodetect(sg_ctx *ctx, const sg_cosme_desc *desc, uint1
 	int rc = sgc_check(ctx, pl, desc, frames, nframes, 0, out);
 	if (rc != SG_OK)
 		return rc;
-	SgDevice &dv = ctx->dev[0];
-	HIPCHK(hipSetDevice(dv.id));
 	const size_t fpix = (size_t)pl.npix * pl.C;
-	size_t batch = std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)1 << 28) / fpix));
-	if (ctx->knobs.cosme_chunk > 0)
-		batch = std::min<size_t>(batch, (size_t)ctx->knobs.cosme_chunk);
-	HIPCHK(ensure(dv.cosme_frames, batch * fpix * sizeof(uint16_t)));
-	uint16_t *d = (uint16_t *)dv.cosme_frames.p;
-	for (int f0 = 0; f0 < nframes; f0 += (int)batch) {
-		const int nf = std::min(nframes - f0, (int)batch);
-		const size_t bytes = (size_t)nf * fpix * sizeof(uint16_t);
-		HIPCHK(hipMemcpyAsync(d, frames + (size_t)f0 * fpix, bytes, hipMemcpyHostToDevice, dv.stream));
+	SgHostBatches hb(ctx);
+	HIPCHK(hb.begin(nframes, fpix, SG_HOST_BUDGET_512M, ctx->knobs.cosme_chunk));
+	while (hb.next()) {
+		HIPCHK(hb.upload(frames));
 		SgCosmePlan bp;
-		rc = sg_cosme_plan(desc, nf, 0, 0, ctx->knobs.cosme_chunk, ctx->knobs.cosme_list, bp);
+		rc = sg_cosme_plan(desc, hb.nf, 0, 0, ctx->knobs.cosme_chunk, ctx->knobs.cosme_list, bp);
 		if (rc != SG_OK)
 			return set_err(ctx, rc, "%s", bp.err);
-		rc = sgc_run(ctx, 0, bp, d, nullptr, out + f0);
+		rc = sgc_run(ctx, 0, bp, hb.d, nullptr, out + hb.f0);
 		if (rc != SG_OK)
 			return rc;
-		HIPCHK(hipMemcpyAsync(frames + (size_t)f0 * fpix, d, bytes, hipMemcpyDeviceToHost, dv.stream));
-		HIPCHK(hipStreamSynchronize(dv.stream));
+		HIPCHK(hipMemcpyAsync(frames + (size_t)hb.f0 * fpix, hb.d, hb.bytes(), hipMemcpyDeviceToHost, hb.dv.stream));
+		HIPCHK(hipStreamSynchronize(hb.dv.stream));
 	}
 	return SG_OK;
 }
 
 extern "C" int sg_cosme_last_times(sg_ctx *ctx, int dev_index, double *stat_ms, double *main_ms, double *resolve_ms,
 		int *rounds, int64_t *reexamined) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	const SgDevice &dv = ctx->dev[dev_index];
 	if (stat_ms)

@@ -21,6 +21,7 @@
 #include <string.h>
 #include "../../include/sirilgpu.h"
 #include "sg_cosme.h"
+#include "sg_host_batch.hpp"
 
 #define SGC_MAX_LAYERS 3
 #define SGC_BINS 65536
@@ -53,10 +54,6 @@ static inline int sgc_fail(SgCosmePlan &p, int code, const char *msg) {
 	return code;
 }
 
-static inline size_t sgc_up16(size_t v) {
-	return (v + 15) & ~(size_t)15;
-}
-
 /* the scratch of `chunk` frames; 0 when their pixel ids do not fit 32 bits */
 static inline size_t sgc_chunk_bytes(SgCosmePlan &p, int64_t chunk, int force_list = 0) {
 	const uint64_t px = (uint64_t)chunk * (uint64_t)p.C * (uint64_t)p.npix;
@@ -64,18 +61,18 @@ static inline size_t sgc_chunk_bytes(SgCosmePlan &p, int64_t chunk, int force_li
 		return 0;
 	p.chunk_pixels = px;
 	p.plane_words = (px + 31) / 32;
-	p.state_bytes = sgc_up16((size_t)px * sizeof(uint16_t));
-	p.plane_bytes = sgc_up16((size_t)p.plane_words * sizeof(uint32_t));
+	p.state_bytes = sg_up16((size_t)px * sizeof(uint16_t));
+	p.plane_bytes = sg_up16((size_t)p.plane_words * sizeof(uint32_t));
 	int64_t cap = (int64_t)(px / 8);
 	if (cap < SGC_MIN_LIST)
 		cap = SGC_MIN_LIST;
 	if (force_list > 0)
 		cap = force_list;
 	p.list_cap = (uint32_t)cap;
-	p.list_bytes = sgc_up16((size_t)cap * sizeof(uint32_t));
+	p.list_bytes = sg_up16((size_t)cap * sizeof(uint32_t));
 	p.hist_bytes = (size_t)chunk * p.C * SGC_BINS * sizeof(uint32_t);
-	p.rule_bytes = sgc_up16((size_t)chunk * p.C * sizeof(sgc_rule));
-	p.count_bytes = sgc_up16((size_t)chunk * 2 * sizeof(uint64_t)) + sgc_up16((SGC_NCOUNT + 1) * sizeof(uint32_t));
+	p.rule_bytes = sg_up16((size_t)chunk * p.C * sizeof(sgc_rule));
+	p.count_bytes = sg_up16((size_t)chunk * 2 * sizeof(uint64_t)) + sg_up16((SGC_NCOUNT + 1) * sizeof(uint32_t));
 	p.total_bytes = p.state_bytes + 4 * p.plane_bytes + 2 * p.list_bytes + p.hist_bytes + p.rule_bytes + p.count_bytes;
 	return p.total_bytes;
 }

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "../../include/sirilgpu.h"
+#include "sg_host_batch.hpp"
 
 #define SG_LIT_THREADS 65536
 
@@ -102,23 +103,27 @@ struct SgDevice {
 	SgBuf io_raw, io_bad;
 	SgBuf warp_tab;		/* sg_warp.hip interpolation table */
 	int warp_tab_interp = -1;
+	/* the staged batch of every host-frame entry (SgHostBatches below).  One buffer serves them all:
+	 * each host entry runs on device 0's own stream and returns synchronised, and this per-device
+	 * state is used by one caller at a time, so no two batches are ever live together */
+	SgBuf host_frames;
 	/* star candidates (sg_findstar.hip): histograms / records / masks / row offsets, the scratch
-	 * detection plane, the candidate list and boxes, host frames of sg_findstar */
-	SgBuf fs_work, fs_plane, fs_out, fs_frames, fs_fit;	/* fs_fit: the fit records of sg_findstar_fit* */
+	 * detection plane, the candidate list and boxes */
+	SgBuf fs_work, fs_plane, fs_out, fs_fit;	/* fs_fit: the fit records of sg_findstar_fit* */
 	/* ECC registration (sg_ecc.hip): the template and the chunk's blurred planes, partial moments,
-	 * states and tickets in one block; host frames of sg_register_ecc_u16 */
-	SgBuf ecc_work, ecc_frames;
+	 * states and tickets in one block */
+	SgBuf ecc_work;
 	double ecc_prep_ms = 0., ecc_iter_ms = 0.;	/* the last ECC call: device spans of its prepare and iteration launches */
 	int ecc_launches = 0;
-	/* automatic cosmetic correction (sg_cosme.hip): one chunk's scratch (sg_cosme_plan.hpp); host
-	 * frames of sg_cosme_autodetect; the last call's device spans */
-	SgBuf cosme_work, cosme_frames;
+	/* automatic cosmetic correction (sg_cosme.hip): one chunk's scratch (sg_cosme_plan.hpp); the
+	 * last call's device spans */
+	SgBuf cosme_work;
 	double cosme_stat_ms = 0., cosme_main_ms = 0., cosme_resolve_ms = 0.;
 	int cosme_rounds = 0;
 	long long cosme_reexamined = 0;
 	/* quality estimate of whole layers (sg_quality.hip): one chunk's scratch (sg_quality_plan.hpp);
-	 * host frames of sg_quality_u16; the last call's device span, route and launches */
-	SgBuf quality_work, quality_frames;
+	 * the last call's device span, route and launches */
+	SgBuf quality_work;
 	double quality_ms = 0.;
 	int quality_route = 0, quality_launches = 0;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
@@ -180,6 +185,7 @@ struct SgKnobs {
 	int quality_route = 0;		/* SG_QUALITY_ROUTE: sg_quality_u16*: 0 = the plan's choice, 1 = the resident route where a frame fits, 2 = the tiled route */
 	int quality_chunk = 0;		/* SG_QUALITY_CHUNK: frames per chunk of sg_quality_u16* (0 = from the byte budget; tests of the chunk loop) */
 	int quality_lds = 0;		/* SG_QUALITY_LDS: the resident route's LDS budget in bytes (0 = 160 KiB; tests move the boundary down to a small frame) */
+	int host_batch = 0;		/* SG_HOST_BATCH: frames per batch of the host-frame entries (0 = from the budget; the smaller of it and a module's chunk knob holds; tests of the batch loop) */
 	int reg_rpb = 4;		/* SG_REG_RPB: rows per forward-row workgroup of the half-spectrum path (1 -> 4: 6.46 -> 5.92 ms registration on configs[1], profiles/r03u_ab_reg_rows.log) */
 	void read() {
 		hist_dbg = sg_env_int("SG_HIST_DBG", 0, 1000, 0);
@@ -231,6 +237,7 @@ struct SgKnobs {
 		reg_qfold = sg_env_int("SG_REG_QFOLD", 0, 63, 12) / 3 * 3;
 		norm_fma = sg_env_int("SG_NORM_FMA", 0, 2, 2);
 		ecc_chunk = sg_env_int("SG_ECC_CHUNK", 1, 65535, 0);
+		host_batch = sg_env_int("SG_HOST_BATCH", 1, 65535, 0);
 	}
 };
 
@@ -278,3 +285,55 @@ static inline hipError_t ensure(SgBuf &b, size_t bytes) {
 	return e;
 }
 
+static inline bool sg_dev_ok(const sg_ctx *ctx, int dev_index) {
+	return ctx && dev_index >= 0 && dev_index < (int)ctx->dev.size();
+}
+
+static inline hipStream_t sg_stream(const SgDevice &dv, void *stream) {
+	return stream ? (hipStream_t)stream : dv.stream;
+}
+
+/* The batch loop of a host-frame entry, on device 0 and its stream: begin() sizes the batch by
+ * sg_host_batch_frames (the cap: the smaller of SG_HOST_BATCH and the module's chunk knob) and lays
+ * out dv.host_frames as `lead_elems` u16 (ECC's reference slot, at lead), the batch's frames (at d)
+ * and, 16-byte aligned behind them, `tail_elems` per frame (findstar's wave planes, at tail); each
+ * next() moves on to frames [f0, f0 + nf). */
+struct SgHostBatches {
+	sg_ctx *ctx;
+	SgDevice &dv;
+	size_t frame_elems = 0;
+	int total = 0, batch = 0, f0 = 0, nf = 0;
+	uint16_t *lead = nullptr, *d = nullptr, *tail = nullptr;
+	explicit SgHostBatches(sg_ctx *c) : ctx(c), dv(c->dev[0]) {}
+	hipError_t begin(int frames, size_t elems, size_t budget, int chunk_knob = 0, size_t lead_elems = 0, size_t tail_elems = 0) {
+		frame_elems = elems;
+		total = frames;
+		const int hk = ctx->knobs.host_batch, cap = hk > 0 && (chunk_knob <= 0 || hk < chunk_knob) ? hk : chunk_knob;
+		batch = (int)sg_host_batch_frames((size_t)frames, elems, budget, (size_t)cap);
+		const size_t raw = (lead_elems + (size_t)batch * elems) * sizeof(uint16_t), fbytes = tail_elems ? sg_up16(raw) : raw;
+		hipError_t e = hipSetDevice(dv.id);
+		if (e == hipSuccess)
+			e = ensure(dv.host_frames, fbytes + (size_t)batch * tail_elems * sizeof(uint16_t));
+		lead = (uint16_t *)dv.host_frames.p;
+		d = lead + lead_elems;
+		tail = tail_elems ? (uint16_t *)((char *)lead + fbytes) : nullptr;
+		return e;
+	}
+	bool next() {
+		f0 += nf;
+		nf = total - f0 < batch ? total - f0 : batch;
+		return nf > 0;
+	}
+	size_t bytes() const {	/* of the batch's frames */
+		return (size_t)nf * frame_elems * sizeof(uint16_t);
+	}
+	/* the batch's whole frames of a tight host sequence */
+	hipError_t upload(const uint16_t *frames) {
+		return hipMemcpyAsync(d, frames + (size_t)f0 * frame_elems, bytes(), hipMemcpyHostToDevice, dv.stream);
+	}
+	/* one W x H layer whose rows lie row_pitch elements apart, tight to dst */
+	hipError_t upload_layer(uint16_t *dst, const uint16_t *src, int W, int H, int64_t row_pitch) {
+		const size_t wbytes = (size_t)W * sizeof(uint16_t);
+		return hipMemcpy2DAsync(dst, wbytes, src, (size_t)row_pitch * sizeof(uint16_t), wbytes, (size_t)H, hipMemcpyHostToDevice, dv.stream);
+	}
+};

@@ -165,19 +165,16 @@ __global__ void __launch_bounds__(SGE_THREADS) k_ecc_iter(SgEccIterParams p) {
 	}
 }
 
-static inline size_t sge_up16(size_t v) {
-	return (v + 15) & ~(size_t)15;
-}
-
+/* frame g's result goes to entry dest[g] of `out` (dest == NULL: entry g) */
 static int sge_run(sg_ctx *ctx, int dev_index, const SgEccPlan &pl, const uint16_t *d_frames, const int *included,
-		const sg_ecc_out *out, void *stream) {
+		const int *dest, const sg_ecc_out *out, void *stream) {
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	const int W = pl.W, H = pl.H, chunk = pl.chunk;
-	const size_t o_tmpl = 0, o_planes = o_tmpl + sge_up16(pl.plane_bytes);
-	const size_t o_part = o_planes + sge_up16(pl.plane_bytes * chunk), o_st = o_part + sge_up16(pl.partial_bytes * chunk);
-	const size_t o_tick = o_st + sge_up16(sizeof(sge_state) * chunk), o_act = o_tick + sge_up16(sizeof(unsigned int) * chunk);
+	const size_t o_tmpl = 0, o_planes = o_tmpl + sg_up16(pl.plane_bytes);
+	const size_t o_part = o_planes + sg_up16(pl.plane_bytes * chunk), o_st = o_part + sg_up16(pl.partial_bytes * chunk);
+	const size_t o_tick = o_st + sg_up16(sizeof(sge_state) * chunk), o_act = o_tick + sg_up16(sizeof(unsigned int) * chunk);
 	HIPCHK(ensure(dv.ecc_work, o_act + 16));
 	char *wk = (char *)dv.ecc_work.p;
 	SgEccPrepParams pp;
@@ -261,18 +258,19 @@ static int sge_run(sg_ctx *ctx, int dev_index, const SgEccPlan &pl, const uint16
 			float dx, dy;
 			int sx, sy;
 			sge_result(&r, &dx, &dy, &sx, &sy);
-			out->shiftx[g] = sx;
-			out->shifty[g] = sy;
+			const int o = dest ? dest[g] : g;
+			out->shiftx[o] = sx;
+			out->shifty[o] = sy;
 			if (out->dx)
-				out->dx[g] = dx;
+				out->dx[o] = dx;
 			if (out->dy)
-				out->dy[g] = dy;
+				out->dy[o] = dy;
 			if (out->rho)
-				out->rho[g] = g == pl.ref_image ? 0.0 : r.rho;
+				out->rho[o] = g == pl.ref_image ? 0.0 : r.rho;
 			if (out->iterations)
-				out->iterations[g] = r.iter;
+				out->iterations[o] = r.iter;
 			if (out->failed)
-				out->failed[g] = r.failed;
+				out->failed[o] = r.failed;
 		}
 	}
 	return SG_OK;
@@ -291,13 +289,13 @@ static int sge_check(sg_ctx *ctx, SgEccPlan &pl, const void *frames, int64_t fra
 extern "C" int sg_register_ecc_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_frames, int64_t frame_pitch,
 		int64_t row_pitch, int W, int H, int nframes, int ref_image, const int *included, const sg_ecc_out *out,
 		void *stream) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	SgEccPlan pl;
 	const int rc = sge_check(ctx, pl, d_frames, frame_pitch, row_pitch, W, H, nframes, ref_image, out);
 	if (rc != SG_OK)
 		return rc;
-	return sge_run(ctx, dev_index, pl, d_frames, included, out, stream);
+	return sge_run(ctx, dev_index, pl, d_frames, included, nullptr, out, stream);
 }
 
 /* host frames: the reference's layer and a batch of frames' layers are uploaded tight, slot 0 the
@@ -311,67 +309,32 @@ extern "C" int sg_register_ecc_u16(sg_ctx *ctx, const uint16_t *frames, int64_t 
 	int rc = sge_check(ctx, pl, frames, frame_pitch, row_pitch, W, H, nframes, ref_image, out);
 	if (rc != SG_OK)
 		return rc;
-	SgDevice &dv = ctx->dev[0];
-	HIPCHK(hipSetDevice(dv.id));
 	const size_t npix = (size_t)W * H;
-	size_t batch = std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)1 << 29) / npix));
-	if (ctx->knobs.ecc_chunk > 0)
-		batch = std::min<size_t>(batch, (size_t)ctx->knobs.ecc_chunk);
-	HIPCHK(ensure(dv.ecc_frames, (batch + 1) * npix * sizeof(uint16_t)));
-	uint16_t *d = (uint16_t *)dv.ecc_frames.p;
-	const size_t wbytes = (size_t)W * sizeof(uint16_t), pbytes = (size_t)pl.row_pitch * sizeof(uint16_t);
-	HIPCHK(hipMemcpy2DAsync(d, wbytes, frames + (int64_t)ref_image * pl.frame_pitch, pbytes, wbytes, (size_t)H,
-			hipMemcpyHostToDevice, dv.stream));
-	std::vector<int> inc(batch + 1), sx(batch + 1), sy(batch + 1), it(batch + 1), fl(batch + 1);
-	std::vector<float> dx(batch + 1), dy(batch + 1);
-	std::vector<double> rho(batch + 1);
-	sg_ecc_out o;
-	o.shiftx = sx.data();
-	o.shifty = sy.data();
-	o.dx = dx.data();
-	o.dy = dy.data();
-	o.rho = rho.data();
-	o.iterations = it.data();
-	o.failed = fl.data();
-	for (int f0 = 0; f0 < nframes; f0 += (int)batch) {
-		const int nf = std::min(nframes - f0, (int)batch);
-		inc[0] = 1;
-		for (int f = 0; f < nf; f++) {
-			const int g = f0 + f;
+	SgHostBatches hb(ctx);
+	HIPCHK(hb.begin(nframes, npix, SG_HOST_BUDGET_1G, ctx->knobs.ecc_chunk, npix));
+	HIPCHK(hb.upload_layer(hb.lead, frames + (int64_t)ref_image * pl.frame_pitch, W, H, pl.row_pitch));
+	std::vector<int> inc(hb.batch + 1), dest(hb.batch + 1);
+	inc[0] = 1;
+	dest[0] = ref_image;	/* each batch writes the reference's own result again: the same values */
+	while (hb.next()) {
+		for (int f = 0; f < hb.nf; f++) {
+			const int g = dest[1 + f] = hb.f0 + f;
 			inc[1 + f] = g != ref_image && (!included || included[g]);
-			HIPCHK(hipMemcpy2DAsync(d + (size_t)(1 + f) * npix, wbytes, frames + (int64_t)g * pl.frame_pitch, pbytes, wbytes,
-					(size_t)H, hipMemcpyHostToDevice, dv.stream));
+			HIPCHK(hb.upload_layer(hb.d + (size_t)f * npix, frames + (int64_t)g * pl.frame_pitch, W, H, pl.row_pitch));
 		}
 		SgEccPlan bp;
-		rc = sg_ecc_plan(W, H, nf + 1, 0, 0, 0, 0, ctx->knobs.ecc_chunk, bp);
+		rc = sg_ecc_plan(W, H, hb.nf + 1, 0, 0, 0, 0, ctx->knobs.ecc_chunk, bp);
 		if (rc != SG_OK)
 			return set_err(ctx, rc, "%s", bp.err);
-		rc = sge_run(ctx, 0, bp, d, inc.data(), &o, nullptr);
+		rc = sge_run(ctx, 0, bp, hb.lead, inc.data(), dest.data(), out, nullptr);
 		if (rc != SG_OK)
 			return rc;
-		for (int f = 0; f < nf; f++) {
-			const int g = f0 + f, k = g == ref_image ? 0 : 1 + f;
-			if (!inc[1 + f] && g != ref_image)
-				continue;
-			out->shiftx[g] = sx[k];
-			out->shifty[g] = sy[k];
-			if (out->dx)
-				out->dx[g] = dx[k];
-			if (out->dy)
-				out->dy[g] = dy[k];
-			if (out->rho)
-				out->rho[g] = rho[k];
-			if (out->iterations)
-				out->iterations[g] = it[k];
-			if (out->failed)
-				out->failed[g] = fl[k];
-		}
 	}
 	return SG_OK;
 }
 
 extern "C" int sg_register_ecc_last_times(sg_ctx *ctx, int dev_index, double *prepare_ms, double *iterate_ms, int *launches) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	const SgDevice &dv = ctx->dev[dev_index];
 	if (prepare_ms)

@@ -448,10 +448,6 @@ __global__ void __launch_bounds__(64) k_starfit_select(SgFitParams p) {
 		p.nstars[f] = (int)(run < (unsigned long long)p.max_stars ? run : (unsigned long long)p.max_stars);
 }
 
-static inline size_t sgf_up16(size_t v) {
-	return (v + 15) & ~(size_t)15;
-}
-
 /* the body of sg_findstar_device; with a fit plan `fp` it goes on, chunk by chunk, to the fit of the
  * stored candidates (nstars, stars, cands of sg_findstar_fit_device; cand_xy and boxes are NULL) */
 static int sgf_run(sg_ctx *ctx, int dev_index, const SgFindstarPlan &pl, const uint16_t *d_frames, int nframes,
@@ -459,18 +455,18 @@ static int sgf_run(sg_ctx *ctx, int dev_index, const SgFindstarPlan &pl, const u
 		void *stream, const SgStarfitPlan *fp, int32_t *nstars, sg_star *stars, sg_starfit_cand *cands) {
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	const int W = pl.W, H = pl.H;
 	const int64_t npix = (int64_t)W * H;
 	if (frame_stride == 0)
 		frame_stride = npix * pl.C;
 	const int chunk = sgf_chunk_frames(pl, nframes, d_wave != nullptr);
 	/* the chunk's work block */
-	const size_t o_hist = 0, o_stat = o_hist + sgf_up16(pl.hist_bytes * chunk);
-	const size_t o_fmax = o_stat + sgf_up16(pl.stat_bytes * chunk), o_thr = o_fmax + sgf_up16(sizeof(uint32_t) * chunk);
-	const size_t o_nst = o_thr + sgf_up16(sizeof(int) * chunk), o_rows = o_nst + sgf_up16(2 * sizeof(uint64_t) * chunk);
-	const size_t o_mask = o_rows + sgf_up16(pl.rows_bytes * chunk), o_tot = o_mask + sgf_up16(pl.mask_bytes * chunk);
-	const size_t work_bytes = o_tot + sgf_up16(sizeof(uint32_t) * chunk);
+	const size_t o_hist = 0, o_stat = o_hist + sg_up16(pl.hist_bytes * chunk);
+	const size_t o_fmax = o_stat + sg_up16(pl.stat_bytes * chunk), o_thr = o_fmax + sg_up16(sizeof(uint32_t) * chunk);
+	const size_t o_nst = o_thr + sg_up16(sizeof(int) * chunk), o_rows = o_nst + sg_up16(2 * sizeof(uint64_t) * chunk);
+	const size_t o_mask = o_rows + sg_up16(pl.rows_bytes * chunk), o_tot = o_mask + sg_up16(pl.mask_bytes * chunk);
+	const size_t work_bytes = o_tot + sg_up16(sizeof(uint32_t) * chunk);
 	HIPCHK(ensure(dv.fs_work, work_bytes));
 	char *wk = (char *)dv.fs_work.p;
 	uint32_t *hist = (uint32_t *)(wk + o_hist), *fmax = (uint32_t *)(wk + o_fmax), *rows = (uint32_t *)(wk + o_rows);
@@ -599,7 +595,7 @@ static int sgf_run(sg_ctx *ctx, int dev_index, const SgFindstarPlan &pl, const u
 		}
 		if (total == 0)
 			continue;
-		const size_t xy_bytes = sgf_up16(total * 2 * sizeof(int32_t));
+		const size_t xy_bytes = sg_up16(total * 2 * sizeof(int32_t));
 		const size_t box_bytes = boxes ? total * (size_t)pl.box_elems * sizeof(uint16_t) : 0;
 		HIPCHK(ensure(dv.fs_out, xy_bytes + box_bytes));
 		kp.xy = (int *)dv.fs_out.p;
@@ -623,9 +619,9 @@ static int sgf_run(sg_ctx *ctx, int dev_index, const SgFindstarPlan &pl, const u
 		}
 		if (fp) {
 			/* the chunk's fit block: medians, star counts, candidate records, compact stars */
-			const size_t o_bg = 0, o_ns = o_bg + sgf_up16(sizeof(double) * nf), o_cd = o_ns + sgf_up16(sizeof(int) * nf);
-			const size_t o_st = o_cd + sgf_up16(total * sizeof(sg_starfit_cand));
-			HIPCHK(ensure(dv.fs_fit, o_st + sgf_up16(total * sizeof(sg_star))));
+			const size_t o_bg = 0, o_ns = o_bg + sg_up16(sizeof(double) * nf), o_cd = o_ns + sg_up16(sizeof(int) * nf);
+			const size_t o_st = o_cd + sg_up16(total * sizeof(sg_starfit_cand));
+			HIPCHK(ensure(dv.fs_fit, o_st + sg_up16(total * sizeof(sg_star))));
 			char *fb = (char *)dv.fs_fit.p;
 			for (int f = 0; f < nf; f++)
 				hmed[f] = rec[f].median;
@@ -678,7 +674,7 @@ static int sgf_run(sg_ctx *ctx, int dev_index, const SgFindstarPlan &pl, const u
 extern "C" int sg_findstar_device(sg_ctx *ctx, int dev_index, const sg_findstar_desc *desc, const uint16_t *d_frames,
 		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *cand_xy, uint16_t *boxes,
 		uint16_t *d_wave, void *stream) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	SgFindstarPlan pl;
 	int rc = sg_findstar_plan(desc, pl);
@@ -704,7 +700,7 @@ static int sgs_check(sg_ctx *ctx, const sg_starfit_desc *desc, SgStarfitPlan &fp
 extern "C" int sg_findstar_fit_device(sg_ctx *ctx, int dev_index, const sg_starfit_desc *desc, const uint16_t *d_frames,
 		int nframes, int64_t frame_stride, sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars,
 		sg_starfit_cand *cands, void *stream) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	SgStarfitPlan fp;
 	const int rc = sgs_check(ctx, desc, fp, d_frames, nframes, per_frame, nstars, stars, cands);
@@ -716,6 +712,30 @@ extern "C" int sg_findstar_fit_device(sg_ctx *ctx, int dev_index, const sg_starf
 			&fp, nstars, stars, fp.want_candidates ? cands : nullptr);
 }
 
+/* the host entries: batches of frames through sgf_run; the plane, when asked for, follows the batch's frames */
+static int sgf_host(sg_ctx *ctx, const SgFindstarPlan &pl, const uint16_t *frames, int nframes, sg_findstar_frame *per_frame,
+		int32_t *cand_xy, uint16_t *boxes, uint16_t *wave, const SgStarfitPlan *fp, int32_t *nstars, sg_star *stars,
+		sg_starfit_cand *cands) {
+	const size_t npix = (size_t)pl.W * pl.H, maxc = (size_t)pl.max_candidates;
+	SgHostBatches hb(ctx);
+	HIPCHK(hb.begin(nframes, npix * pl.C, SG_HOST_BUDGET_1G, 0, 0, wave ? npix : 0));
+	while (hb.next()) {
+		const size_t f0 = (size_t)hb.f0;
+		HIPCHK(hb.upload(frames));
+		const int rc = sgf_run(ctx, 0, pl, hb.d, hb.nf, 0, per_frame + f0, cand_xy ? cand_xy + f0 * maxc * 2 : nullptr,
+				boxes ? boxes + f0 * maxc * (size_t)pl.box_elems : nullptr, hb.tail, nullptr, fp, nstars ? nstars + f0 : nullptr,
+				stars ? stars + f0 * (size_t)fp->max_stars : nullptr, cands ? cands + f0 * maxc : nullptr);
+		if (rc != SG_OK)
+			return rc;
+		if (wave) {
+			HIPCHK(hipMemcpyAsync(wave + f0 * npix, hb.tail, (size_t)hb.nf * npix * sizeof(uint16_t), hipMemcpyDeviceToHost,
+					hb.dv.stream));
+			HIPCHK(hipStreamSynchronize(hb.dv.stream));
+		}
+	}
+	return SG_OK;
+}
+
 extern "C" int sg_findstar_fit(sg_ctx *ctx, const sg_starfit_desc *desc, const uint16_t *frames, int nframes,
 		sg_findstar_frame *per_frame, int32_t *nstars, sg_star *stars, sg_starfit_cand *cands) {
 	if (!ctx || ctx->dev.empty())
@@ -724,24 +744,8 @@ extern "C" int sg_findstar_fit(sg_ctx *ctx, const sg_starfit_desc *desc, const u
 	int rc = sgs_check(ctx, desc, fp, frames, nframes, per_frame, nstars, stars, cands);
 	if (rc != SG_OK)
 		return rc;
-	const SgFindstarPlan &pl = fp.find;
-	SgDevice &dv = ctx->dev[0];
-	HIPCHK(hipSetDevice(dv.id));
-	const size_t total = (size_t)pl.W * pl.H * pl.C;
-	const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)1 << 29) / total));
-	HIPCHK(ensure(dv.fs_frames, (size_t)batch * total * sizeof(uint16_t)));
-	uint16_t *d = (uint16_t *)dv.fs_frames.p;
-	for (int f0 = 0; f0 < nframes; f0 += batch) {
-		const int nf = std::min(nframes - f0, batch);
-		HIPCHK(hipMemcpyAsync(d, frames + (size_t)f0 * total, (size_t)nf * total * sizeof(uint16_t), hipMemcpyHostToDevice,
-				dv.stream));
-		rc = sgf_run(ctx, 0, pl, d, nf, 0, per_frame + f0, nullptr, nullptr, nullptr, nullptr, &fp, nstars + f0,
-				stars ? stars + (size_t)f0 * fp.max_stars : nullptr,
-				fp.want_candidates && cands ? cands + (size_t)f0 * pl.max_candidates : nullptr);
-		if (rc != SG_OK)
-			return rc;
-	}
-	return SG_OK;
+	return sgf_host(ctx, fp.find, frames, nframes, per_frame, nullptr, nullptr, nullptr, &fp, nstars, stars,
+			fp.want_candidates ? cands : nullptr);
 }
 
 extern "C" int sg_findstar(sg_ctx *ctx, const sg_findstar_desc *desc, const uint16_t *frames, int nframes,
@@ -754,28 +758,5 @@ extern "C" int sg_findstar(sg_ctx *ctx, const sg_findstar_desc *desc, const uint
 		return set_err(ctx, rc, "%s", pl.err);
 	if (!frames || nframes < 1 || !per_frame || (pl.max_candidates > 0 && !cand_xy))
 		return set_err(ctx, SG_ERR_GENERIC, "findstar: missing frames, records or candidate array%s", "");
-	SgDevice &dv = ctx->dev[0];
-	HIPCHK(hipSetDevice(dv.id));
-	const size_t npix = (size_t)pl.W * pl.H, total = npix * pl.C;
-	/* batches of at most 1 GiB of frames; the plane, when asked for, follows the frames */
-	const int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)nframes, ((size_t)1 << 29) / total));
-	const size_t fbytes = sgf_up16((size_t)batch * total * sizeof(uint16_t));
-	HIPCHK(ensure(dv.fs_frames, fbytes + (wave ? (size_t)batch * npix * sizeof(uint16_t) : 0)));
-	uint16_t *d = (uint16_t *)dv.fs_frames.p, *dw = wave ? (uint16_t *)((char *)dv.fs_frames.p + fbytes) : nullptr;
-	for (int f0 = 0; f0 < nframes; f0 += batch) {
-		const int nf = std::min(nframes - f0, batch);
-		HIPCHK(hipMemcpyAsync(d, frames + (size_t)f0 * total, (size_t)nf * total * sizeof(uint16_t), hipMemcpyHostToDevice,
-				dv.stream));
-		rc = sg_findstar_device(ctx, 0, desc, d, nf, 0, per_frame + f0,
-				cand_xy ? cand_xy + (size_t)f0 * pl.max_candidates * 2 : nullptr,
-				boxes ? boxes + (size_t)f0 * pl.max_candidates * (size_t)pl.box_elems : nullptr, dw, nullptr);
-		if (rc != SG_OK)
-			return rc;
-		if (wave) {
-			HIPCHK(hipMemcpyAsync(wave + (size_t)f0 * npix, dw, (size_t)nf * npix * sizeof(uint16_t), hipMemcpyDeviceToHost,
-					dv.stream));
-			HIPCHK(hipStreamSynchronize(dv.stream));
-		}
-	}
-	return SG_OK;
+	return sgf_host(ctx, pl, frames, nframes, per_frame, cand_xy, boxes, wave, nullptr, nullptr, nullptr, nullptr);
 }

@@ -307,7 +307,7 @@ struct sg_prepro {
 	SgPreproPlan plan;
 	uint16_t *d_off = nullptr, *d_dark = nullptr, *d_flat = nullptr, *d_darkfit = nullptr;
 	uint32_t *d_items = nullptr, *d_comp_start = nullptr;
-	SgBuf work, host_frames;
+	SgBuf work;
 	void *pin = nullptr;	/* pinned: the row results of one batch of evaluations */
 	size_t pin_size = 0;
 };
@@ -317,8 +317,7 @@ extern "C" void sg_prepro_free(sg_prepro *pp) {
 		return;
 	if (pp->ctx && pp->dev_index < (int)pp->ctx->dev.size())
 		(void)hipSetDevice(pp->ctx->dev[pp->dev_index].id);
-	void *bufs[] = {pp->d_off, pp->d_dark, pp->d_flat, pp->d_darkfit, pp->d_items, pp->d_comp_start, pp->work.p,
-		pp->host_frames.p};
+	void *bufs[] = {pp->d_off, pp->d_dark, pp->d_flat, pp->d_darkfit, pp->d_items, pp->d_comp_start, pp->work.p};
 	for (void *b : bufs)
 		if (b)
 			(void)hipFree(b);
@@ -354,7 +353,7 @@ static int sgp_create(sg_ctx *ctx, sg_prepro *pp, const sg_prepro_desc *desc, hi
 }
 
 extern "C" int sg_prepro_create(sg_ctx *ctx, int dev_index, const sg_prepro_desc *desc, sg_prepro **out) {
-	if (!ctx || !out || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index) || !out)
 		return SG_ERR_GENERIC;
 	*out = nullptr;
 	sg_prepro *pp = new sg_prepro;
@@ -460,7 +459,7 @@ static int sgp_run_noise(sg_ctx *ctx, sg_prepro *pp, hipStream_t s, const uint16
 }
 
 static int sgp_check_call(sg_ctx *ctx, int dev_index, const sg_prepro *pp, const void *d_frames, int nframes) {
-	if (!ctx || !pp || !d_frames || nframes < 1 || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index) || !pp || !d_frames || nframes < 1)
 		return SG_ERR_GENERIC;
 	if (pp->ctx != ctx || pp->dev_index != dev_index)
 		return set_err(ctx, SG_ERR_GENERIC, "the preprocessing object was created for another context or device%s", "");
@@ -478,7 +477,7 @@ extern "C" int sg_prepro_noise_device(sg_ctx *ctx, int dev_index, sg_prepro *pp,
 		return set_err(ctx, SG_ERR_GENERIC, "the noise of a dark-subtracted frame needs a master dark%s", "");
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	const SgPreproPlan &pl = pp->plan;
 	if (frame_stride == 0)
 		frame_stride = (int64_t)pl.C * pl.H * pl.W;
@@ -505,7 +504,7 @@ extern "C" int sg_prepro_frames_device(sg_ctx *ctx, int dev_index, sg_prepro *pp
 		return rc;
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	const SgPreproPlan &pl = pp->plan;
 	const int64_t total = (int64_t)pl.C * pl.H * pl.W;
 	if (frame_stride == 0)
@@ -596,21 +595,16 @@ extern "C" int sg_prepro_frames(sg_ctx *ctx, sg_prepro *pp, uint16_t *frames, in
 	int rc = sgp_check_call(ctx, 0, pp, frames, nframes);
 	if (rc != SG_OK)
 		return rc;
-	SgDevice &dv = ctx->dev[0];
-	HIPCHK(hipSetDevice(dv.id));
 	const size_t total = (size_t)pp->plan.C * pp->plan.H * pp->plan.W;
-	/* batches of at most 1 GiB, through the object's own frame buffer */
-	const int batch = (int)std::max<size_t>(1, std::min<size_t>(SGP_CHUNK_FRAMES, ((size_t)1 << 29) / total));
-	for (int f0 = 0; f0 < nframes; f0 += batch) {
-		const int nf = std::min(nframes - f0, batch);
-		const size_t bytes = (size_t)nf * total * sizeof(uint16_t);
-		HIPCHK(ensure(pp->host_frames, (size_t)batch * total * sizeof(uint16_t)));
-		uint16_t *d = (uint16_t *)pp->host_frames.p;
-		HIPCHK(hipMemcpyAsync(d, frames + (size_t)f0 * total, bytes, hipMemcpyHostToDevice, dv.stream));
-		if ((rc = sg_prepro_frames_device(ctx, 0, pp, d, nf, 0, dark_k ? dark_k + f0 : nullptr, nullptr)) != SG_OK)
+	/* a batch is at most one chunk of the device entry */
+	SgHostBatches hb(ctx);
+	HIPCHK(hb.begin(nframes, total, SG_HOST_BUDGET_1G, SGP_CHUNK_FRAMES));
+	while (hb.next()) {
+		HIPCHK(hb.upload(frames));
+		if ((rc = sg_prepro_frames_device(ctx, 0, pp, hb.d, hb.nf, 0, dark_k ? dark_k + hb.f0 : nullptr, nullptr)) != SG_OK)
 			return rc;
-		HIPCHK(hipMemcpyAsync(frames + (size_t)f0 * total, d, bytes, hipMemcpyDeviceToHost, dv.stream));
-		HIPCHK(hipStreamSynchronize(dv.stream));
+		HIPCHK(hipMemcpyAsync(frames + (size_t)hb.f0 * total, hb.d, hb.bytes(), hipMemcpyDeviceToHost, hb.dv.stream));
+		HIPCHK(hipStreamSynchronize(hb.dv.stream));
 	}
 	return SG_OK;
 }

@@ -191,22 +191,24 @@ __global__ void __launch_bounds__(SGQ_THREADS) k_qest_finish(SgQualityParams p, 
 		p.out[i] = sgq_finish(p.acc[i].val, p.acc[i].pixels);
 }
 
-/* work: the frames to estimate, in index order; their results go to quality_raw[work[k]] */
+/* work: the frames to estimate, in index order; their results go to quality_raw[dest[k]] (dest == NULL: work[k]) */
 static int sgq_run(sg_ctx *ctx, int dev_index, const SgQualityPlan &pl, const uint16_t *d_frames, const std::vector<int> &work,
-		double *quality_raw, void *stream) {
+		const int *dest, double *quality_raw, void *stream) {
+	if (!dest)
+		dest = work.data();
 	SgDevice &dv = ctx->dev[dev_index];
 	dv.quality_ms = 0.;
 	dv.quality_route = pl.route;
 	dv.quality_launches = 0;
 	if (pl.route == SGQ_ROUTE_NONE) {
-		for (int f : work)
-			quality_raw[f] = 0.0;
+		for (size_t k = 0; k < work.size(); k++)
+			quality_raw[dest[k]] = 0.0;
 		return SG_OK;
 	}
 	if (work.empty())
 		return SG_OK;
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	HIPCHK(ensure(dv.quality_work, pl.total_bytes + 64));
 	if (pl.route == SGQ_ROUTE_RESIDENT)
 		HIPCHK(hipFuncSetAttribute((const void *)k_qest_resident, hipFuncAttributeMaxDynamicSharedMemorySize, SGQ_LDS_MAX));
@@ -251,7 +253,7 @@ static int sgq_run(sg_ctx *ctx, int dev_index, const SgQualityPlan &pl, const ui
 		HIPCHK(hipEventElapsedTime(&ms, dv.ev[0], dv.ev[1]));
 		dv.quality_ms += ms;
 		for (int k = 0; k < nf; k++)
-			quality_raw[work[k0 + k]] = hout[k];
+			quality_raw[dest[k0 + k]] = hout[k];
 	}
 	return SG_OK;
 }
@@ -278,17 +280,17 @@ static int sgq_check(sg_ctx *ctx, SgQualityPlan &pl, std::vector<int> &work, con
 
 extern "C" int sg_quality_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_frames, int64_t frame_pitch,
 		int64_t row_pitch, int W, int H, int nframes, const int *included, double *quality_raw, void *stream) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	SgQualityPlan pl;
 	std::vector<int> work;
 	const int rc = sgq_check(ctx, pl, work, d_frames, frame_pitch, row_pitch, W, H, nframes, included, quality_raw);
 	if (rc != SG_OK)
 		return rc;
-	return sgq_run(ctx, dev_index, pl, d_frames, work, quality_raw, stream);
+	return sgq_run(ctx, dev_index, pl, d_frames, work, nullptr, quality_raw, stream);
 }
 
-/* host frames: the included frames are uploaded tight in batches of at most 512 MB and estimated as
+/* host frames: the included frames are uploaded tight in batches of at most 512 MiB and estimated as
  * a sequence of their own; a frame's result does not depend on its neighbours, so this equals the
  * device entry.  The timings of sg_quality_last_times are summed over the batches. */
 extern "C" int sg_quality_u16(sg_ctx *ctx, const uint16_t *frames, int64_t frame_pitch, int64_t row_pitch, int W, int H,
@@ -300,47 +302,37 @@ extern "C" int sg_quality_u16(sg_ctx *ctx, const uint16_t *frames, int64_t frame
 	int rc = sgq_check(ctx, pl, work, frames, frame_pitch, row_pitch, W, H, nframes, included, quality_raw);
 	if (rc != SG_OK)
 		return rc;
-	SgDevice &dv = ctx->dev[0];
 	if (pl.route == SGQ_ROUTE_NONE || work.empty())
-		return sgq_run(ctx, 0, pl, nullptr, work, quality_raw, nullptr);
-	HIPCHK(hipSetDevice(dv.id));
+		return sgq_run(ctx, 0, pl, nullptr, work, nullptr, quality_raw, nullptr);
 	const size_t npix = (size_t)W * H;
-	size_t batch = std::max<size_t>(1, std::min<size_t>(work.size(), ((size_t)1 << 28) / npix));
-	if (ctx->knobs.quality_chunk > 0)
-		batch = std::min<size_t>(batch, (size_t)ctx->knobs.quality_chunk);
-	HIPCHK(ensure(dv.quality_frames, batch * npix * sizeof(uint16_t)));
-	uint16_t *d = (uint16_t *)dv.quality_frames.p;
-	const size_t wbytes = (size_t)W * sizeof(uint16_t), pbytes = (size_t)pl.row_pitch * sizeof(uint16_t);
-	std::vector<int> seq(batch);
-	std::vector<double> q(batch);
+	SgHostBatches hb(ctx);
+	HIPCHK(hb.begin((int)work.size(), npix, SG_HOST_BUDGET_512M, ctx->knobs.quality_chunk));
+	std::vector<int> seq(hb.batch);
 	double ms = 0.;
 	int launches = 0;
-	for (size_t k0 = 0; k0 < work.size(); k0 += batch) {
-		const int nf = (int)std::min(work.size() - k0, batch);
+	while (hb.next()) {
+		const int k0 = hb.f0, nf = hb.nf;
 		for (int k = 0; k < nf; k++) {
 			seq[k] = k;
-			HIPCHK(hipMemcpy2DAsync(d + (size_t)k * npix, wbytes, frames + (int64_t)work[k0 + k] * pl.frame_pitch, pbytes, wbytes,
-					(size_t)H, hipMemcpyHostToDevice, dv.stream));
+			HIPCHK(hb.upload_layer(hb.d + (size_t)k * npix, frames + (int64_t)work[k0 + k] * pl.frame_pitch, W, H, pl.row_pitch));
 		}
 		SgQualityPlan bp;
 		rc = sg_quality_plan(W, H, nf, nf, 0, 0, 0, ctx->knobs.quality_route, ctx->knobs.quality_chunk, ctx->knobs.quality_lds, bp);
 		if (rc != SG_OK)
 			return set_err(ctx, rc, "%s", bp.err);
-		rc = sgq_run(ctx, 0, bp, d, std::vector<int>(seq.begin(), seq.begin() + nf), q.data(), nullptr);
+		rc = sgq_run(ctx, 0, bp, hb.d, std::vector<int>(seq.begin(), seq.begin() + nf), work.data() + k0, quality_raw, nullptr);
 		if (rc != SG_OK)
 			return rc;
-		ms += dv.quality_ms;
-		launches += dv.quality_launches;
-		for (int k = 0; k < nf; k++)
-			quality_raw[work[k0 + k]] = q[k];
+		ms += hb.dv.quality_ms;
+		launches += hb.dv.quality_launches;
 	}
-	dv.quality_ms = ms;
-	dv.quality_launches = launches;
+	hb.dv.quality_ms = ms;
+	hb.dv.quality_launches = launches;
 	return SG_OK;
 }
 
 extern "C" int sg_quality_last_times(sg_ctx *ctx, int dev_index, double *ms, int *route, int *launches) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size())
+	if (!sg_dev_ok(ctx, dev_index))
 		return SG_ERR_GENERIC;
 	const SgDevice &dv = ctx->dev[dev_index];
 	if (ms)

@@ -26,6 +26,7 @@
 #include <vector>
 #include "../../include/sirilgpu.h"
 #include "sg_quality.h"
+#include "sg_host_batch.hpp"
 
 #define SGQ_ROUTE_NONE 0
 #define SGQ_ROUTE_RESIDENT 1
@@ -60,13 +61,9 @@ static inline int sgq_fail(SgQualityPlan &p, int code, const char *msg) {
 	return code;
 }
 
-static inline size_t sgq_up16(size_t v) {
-	return (v + 15) & ~(size_t)15;
-}
-
 static inline size_t sgq_chunk_bytes(SgQualityPlan &p, int64_t chunk) {
-	p.list_bytes = sgq_up16((size_t)chunk * sizeof(int32_t));
-	p.out_bytes = sgq_up16((size_t)chunk * sizeof(double));
+	p.list_bytes = sg_up16((size_t)chunk * sizeof(int32_t));
+	p.out_bytes = sg_up16((size_t)chunk * sizeof(double));
 	p.planes_bytes = p.route == SGQ_ROUTE_TILED ? (size_t)chunk * p.plane_bytes : 0;
 	p.acc_bytes = p.route == SGQ_ROUTE_TILED ? (size_t)chunk * SGQ_ACC_BYTES : 0;
 	p.total_bytes = p.list_bytes + p.out_bytes + p.planes_bytes + p.acc_bytes;
@@ -106,7 +103,7 @@ static inline int sg_quality_plan(int W, int H, int nframes, int nwork, int64_t 
 	if (p.g.xs < 2 || p.g.ys < 2)
 		return SG_OK;	/* route none: 0.0 for every frame, nothing launched */
 	p.nsamples = (int64_t)p.g.xs * p.g.ys;
-	p.plane_bytes = sgq_up16((size_t)p.nsamples * sizeof(uint16_t));
+	p.plane_bytes = sg_up16((size_t)p.nsamples * sizeof(uint16_t));
 	p.lds_bytes = 2 * p.plane_bytes + SGQ_LDS_TAIL;
 	p.resident_fits = p.nsamples <= p.resident_max_samples;
 	p.route = force_route != SGQ_ROUTE_TILED && p.resident_fits ? SGQ_ROUTE_RESIDENT : SGQ_ROUTE_TILED;

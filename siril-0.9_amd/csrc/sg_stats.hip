@@ -100,12 +100,12 @@ k_ikss_solve(const uint32_t *__restrict__ P, const uint32_t *__restrict__ maxi, 
 
 extern "C" int sg_frame_stats_ikss_device(sg_ctx *ctx, int dev_index, const uint16_t *d_frames, int nframes, int C,
 		int H, int W, int64_t frame_stride, double *location, double *scale, void *stream) {
-	if (!ctx || dev_index < 0 || dev_index >= (int)ctx->dev.size() || !d_frames || nframes < 1 || C < 1 || C > 3 ||
+	if (!sg_dev_ok(ctx, dev_index) || !d_frames || nframes < 1 || C < 1 || C > 3 ||
 			H < 1 || W < 1 || !location || !scale)
 		return SG_ERR_GENERIC;
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	const int64_t npix = (int64_t)H * W;
 	if (frame_stride == 0)
 		frame_stride = npix * C;

@@ -199,13 +199,13 @@ static int sg_invert3(const double *a, double *o) {
 extern "C" int sg_warp_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_in, int width, int height,
 		int nb_layers, uint16_t *d_out, int out_width, int out_height, const double *hom, int interpolation,
 		void *stream) {
-	if (!ctx || !d_in || !d_out || !hom || dev_index < 0 || dev_index >= (int)ctx->dev.size() || width <= 0 ||
+	if (!sg_dev_ok(ctx, dev_index) || !d_in || !d_out || !hom || width <= 0 ||
 			height <= 0 || out_width <= 0 || out_height <= 0 || nb_layers < 1 || nb_layers > 3 ||
 			interpolation < 0 || interpolation > SG_WARP_LANCZOS4)
 		return SG_ERR_GENERIC;
 	SgDevice &dv = ctx->dev[dev_index];
 	HIPCHK(hipSetDevice(dv.id));
-	hipStream_t s = stream ? (hipStream_t)stream : dv.stream;
+	hipStream_t s = sg_stream(dv, stream);
 	const int interp = interpolation == SG_WARP_AREA ? SG_WARP_LINEAR : interpolation;
 	SgWarp w;
 	if (!sg_invert3(hom, w.M)) {

@@ -79,8 +79,9 @@ def test_prepro_chunks_against_the_frame_counts():
     chunk = _one(r"#define SGP_CHUNK_FRAMES (\d+)", _source("sg_prepro.hip"))
     assert ppr.BATCH_FRAMES == 2 * chunk + 1            # frames 128 and 256 open the second and third chunk
     assert ppr.BATCH_FRAMES_RGB == chunk + 1
-    # the host entry's batch is the same number for small frames
-    assert "std::min<size_t>(SGP_CHUNK_FRAMES, ((size_t)1 << 29) / total)" in _source("sg_prepro.hip")
+    # the host entry's batch is the same number for small frames: the shared loop capped by the chunk
+    # (tests/test_host_batch_cpu.py pins the rule: 257 frames of this shape under that cap go 128 at a time)
+    assert "hb.begin(nframes, total, SG_HOST_BUDGET_1G, SGP_CHUNK_FRAMES)" in _source("sg_prepro.hip")
 
 
 def test_large_frames_pass_the_capped_grids():
