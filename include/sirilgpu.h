@@ -282,6 +282,51 @@ int sg_warp_u16_device(sg_ctx *ctx, int dev_index, const uint16_t *d_in, int wid
 		int interpolation, void *stream);
 
 /*
+ * The same warp on a whole resident sequence, one homography per frame: the loop body of
+ * register_star_alignment after the matching (src/registration/registration.c:655-755), which
+ * warps every layer of every frame and writes the compacted r_ sequence.  Frame f of the source is
+ * nb_layers planes of width x height at d_in + f * frame_pitch elements (0 = tight); hom holds
+ * nframes x 9 doubles (h00..h22 per frame, host memory).  action[f] (host, NULL = all APPLY):
+ *   SG_WARP_SKIP   the frame is excluded, has too few stars or its match failed: nothing is written;
+ *   SG_WARP_APPLY  the frame is warped;
+ *   SG_WARP_COPY   the reference frame, saved unwarped (:678); needs equal source and output sizes.
+ * out_slot[f] (host, NULL = f) is the output frame the result goes to, the reference's
+ * frame - failed - skipped, at d_out + out_slot[f] * out_frame_pitch elements.  Every byte of a
+ * written frame equals what sg_warp_u16_device gives for that frame and homography (a singular
+ * homography is a zero matrix there too).
+ * Refused before any device work, with a message for sg_last_error: SG_ERR_SIZE for a dimension
+ * <= 0, a plane of 2^31 pixels or more, nb_layers outside 1..3, nframes < 1, a pitch below one
+ * frame; SG_ERR_GENERIC for a missing pointer, an interpolation outside 0..4, an unknown action, COPY
+ * with unequal sizes, a slot below 0 on a written frame, two written frames with one slot, and
+ * source and output byte ranges that overlap.
+ * With a stream the device entry returns once its work is queued on it.  sg_warp_frames_u16 takes
+ * host sequences (the pitches then apply to them), staged in batches of at most 1 GiB of source
+ * frames (SG_HOST_BATCH caps the frames per batch).
+ * sg_warp_frames_last_times waits for the last call on that device and gives its device span, its
+ * kernel launches, the destination tiles that took their taps from LDS and from global memory, and
+ * the pixels of LDS tiles whose window lay outside the staged box and were read from global memory
+ * (0 unless the footprint bound of csrc/sg_warp_tile.h is wrong: speed, never the result, depends
+ * on it).  By default linear and Lanczos-4 take the LDS route, nearest and cubic read global memory
+ * (the measured faster way of each).  Environment knob, read at sg_init: SG_WARP_ROUTE=1 sends every
+ * tile to global memory, 2 every tile whose box fits to LDS, whatever the interpolation.
+ */
+typedef struct sg_warp_seq_desc {
+	int width, height, nb_layers;		/* source frames: planar, memory order (bottom-up), 1..3 layers */
+	int out_width, out_height;		/* ref.x, ref.y */
+	int interpolation;			/* opencv_interpolation 0..4, 2 (area) = linear, as sg_warp_u16 */
+	int64_t frame_pitch, out_frame_pitch;	/* elements between frames, 0 = tight */
+} sg_warp_seq_desc;
+
+enum { SG_WARP_SKIP = 0, SG_WARP_APPLY = 1, SG_WARP_COPY = 2 };
+
+int sg_warp_frames_u16_device(sg_ctx *ctx, int dev_index, const sg_warp_seq_desc *desc, const uint16_t *d_in, int nframes,
+		const double *hom, const int *action, const int *out_slot, uint16_t *d_out, void *stream);
+int sg_warp_frames_u16(sg_ctx *ctx, const sg_warp_seq_desc *desc, const uint16_t *in, int nframes, const double *hom,
+		const int *action, const int *out_slot, uint16_t *out);
+int sg_warp_frames_last_times(sg_ctx *ctx, int dev_index, double *ms, int *launches, uint64_t *tiles_lds,
+		uint64_t *tiles_gather, uint64_t *pixels_stray);
+
+/*
  * Sequence preprocessing: replaces the loop body of seqpreprocess (src/core/siril.c:1019-1169):
  * darkOptimization (:963-985), preprocess (:945-961: imoper SUB :150-187, fdiv :252-275) and
  * cosmeticCorrection (src/algos/cosmetic_correction.c:275-294), on frames resident in HBM, in

@@ -103,6 +103,14 @@ struct SgDevice {
 	SgBuf io_raw, io_bad;
 	SgBuf warp_tab;		/* sg_warp.hip interpolation table */
 	int warp_tab_interp = -1;
+	/* sequence warp (sg_warp.hip, sg_warp_plan.hpp): the counters and the per-frame table; the last
+	 * call's span lies between warp_ev[0] and [1] until warp_pending is folded into warp_ms */
+	SgBuf warp_work;
+	std::vector<unsigned char> warp_table_h;	/* the table's host copy: its upload may read it after the call has returned */
+	hipEvent_t warp_ev[2] = {nullptr, nullptr};
+	bool warp_pending = false;
+	double warp_ms = 0.;
+	int warp_launches = 0;
 	/* the staged batch of every host-frame entry (SgHostBatches below).  One buffer serves them all:
 	 * each host entry runs on device 0's own stream and returns synchronised, and this per-device
 	 * state is used by one caller at a time, so no two batches are ever live together */
@@ -186,6 +194,7 @@ struct SgKnobs {
 	int quality_chunk = 0;		/* SG_QUALITY_CHUNK: frames per chunk of sg_quality_u16* (0 = from the byte budget; tests of the chunk loop) */
 	int quality_lds = 0;		/* SG_QUALITY_LDS: the resident route's LDS budget in bytes (0 = 160 KiB; tests move the boundary down to a small frame) */
 	int host_batch = 0;		/* SG_HOST_BATCH: frames per batch of the host-frame entries (0 = from the budget; the smaller of it and a module's chunk knob holds; tests of the batch loop) */
+	int warp_route = 0;		/* SG_WARP_ROUTE: sg_warp_frames_u16*: 0 = the plan's choice (linear and Lanczos-4: a tile's taps from LDS where its source box fits; nearest and cubic: global memory, profiles/warp_frames_64x4096.log), 1 = every tile reads global memory, 2 = LDS where the box fits for every interpolation (tests and the A/B) */
 	int reg_rpb = 4;		/* SG_REG_RPB: rows per forward-row workgroup of the half-spectrum path (1 -> 4: 6.46 -> 5.92 ms registration on configs[1], profiles/r03u_ab_reg_rows.log) */
 	void read() {
 		hist_dbg = sg_env_int("SG_HIST_DBG", 0, 1000, 0);
@@ -238,6 +247,7 @@ struct SgKnobs {
 		norm_fma = sg_env_int("SG_NORM_FMA", 0, 2, 2);
 		ecc_chunk = sg_env_int("SG_ECC_CHUNK", 1, 65535, 0);
 		host_batch = sg_env_int("SG_HOST_BATCH", 1, 65535, 0);
+		warp_route = sg_env_int("SG_WARP_ROUTE", 0, 2, 0);
 	}
 };
 

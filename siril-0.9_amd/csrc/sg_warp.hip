@@ -276,3 +276,311 @@ extern "C" int sg_warp_u16(sg_ctx *ctx, const uint16_t *in, int width, int heigh
 	HIPCHK(hipStreamSynchronize(dv.stream));
 	return SG_OK;
 }
+
+/*
+ * The same warp on a whole resident sequence (sg_warp_frames_u16*): one launch covers every layer of
+ * every frame of a chunk, the inverse matrices come from a per-frame table in device memory
+ * (sg_warp_plan.hpp), and a workgroup takes one SGW_TILE_X x SGW_TILE_Y destination tile.  It bounds
+ * the tile's source box from the tile's corners (sg_warp_tile.h: the derivation), stages the box into
+ * LDS with coalesced row loads (0 outside the image) and every pixel takes its taps from there; a
+ * tile whose box does not fit, or which the horizon crosses, reads global memory as k_warp does,
+ * and so does any single pixel whose own window is not inside the staged box.  Nearest and cubic
+ * send every tile to global memory by default: there the LDS route lost its A/B (sg_warp_plan.hpp).  The per-pixel
+ * arithmetic is sg_warp_tile.h's restatement of k_warp's, the float sums in the same order, so the
+ * bytes are those of sg_warp_u16_device whatever the route.
+ */
+#include "sg_warp_plan.hpp"
+
+struct SgWarpSeq {
+	const uint16_t *in;
+	uint16_t *out;
+	int W, H, C, oW, oH;
+	int64_t in_plane, out_plane, fpitch, opitch;
+	int bw, f0, force_gather, lds_samples;
+	const float *tab;		/* [1024][K * K] */
+	const SgWarpEntry *table;	/* of the whole call */
+	unsigned long long *ctr;	/* SGW_CTR_SHARDS x {tiles_lds, tiles_gather, pixels_stray} */
+};
+
+struct SgWarpGlobalSrc {
+	const uint16_t *plane;
+	int W, H;
+	__device__ float operator()(int x, int y) const {
+		if ((unsigned)x >= (unsigned)W || (unsigned)y >= (unsigned)H)
+			return 0.f;
+		return (float)plane[(int64_t)(H - 1 - y) * W + x];
+	}
+};
+
+struct SgWarpLdsSrc {
+	const uint16_t *stage;
+	int x0, y0, pitch;
+	__device__ float operator()(int x, int y) const {
+		return (float)stage[(y - y0) * pitch + (x - x0)];
+	}
+};
+
+template <int K> __global__ void __launch_bounds__(SGW_THREADS) k_warp_seq(SgWarpSeq p) {
+	__shared__ uint16_t stage[SGW_LDS_SAMPLES];
+	__shared__ sgw_box sbox;
+	const int fl = (int)blockIdx.z / p.C, c = (int)blockIdx.z - fl * p.C, f = p.f0 + fl;
+	const SgWarpEntry &e = p.table[f];
+	if (e.action != SG_WARP_APPLY)
+		return;
+	double M[9];
+#pragma unroll
+	for (int i = 0; i < 9; i++)
+		M[i] = e.M[i];
+	const int tx0 = (int)blockIdx.x * SGW_TILE_X, ty0 = (int)blockIdx.y * SGW_TILE_Y;
+	const int tx1 = min(tx0 + SGW_TILE_X, p.oW) - 1, ty1 = min(ty0 + SGW_TILE_Y, p.oH) - 1;
+	/* the counters are sharded by workgroup: a million adds to one address would serialise in the L2
+	 * and set the kernel's time (measured: 12.7 ms for 64 x 4096^2 whatever the interpolation) */
+	unsigned long long *ctr = p.ctr + (size_t)((blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * 37u) % SGW_CTR_SHARDS) * SGW_CTR_STRIDE;
+	if (threadIdx.x == 0) {
+		const sgw_box fb = sgw_footprint(M, K, tx0, ty0, tx1, ty1, p.W, p.H, p.lds_samples, p.force_gather);
+		sbox = fb;
+		atomicAdd(&ctr[fb.route == SGW_ROUTE_LDS ? 0 : 1], 1ull);
+	}
+	__syncthreads();
+	const sgw_box b = sbox;
+	const bool lds = b.route == SGW_ROUTE_LDS;
+	const uint16_t *plane = p.in + (int64_t)f * p.fpitch + (int64_t)c * p.in_plane;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	if (lds) {
+		const int w = b.x1 - b.x0 + 1, h = b.y1 - b.y0 + 1;	/* either may be <= 0: nothing staged */
+		for (int r = wave; r < h; r += SGW_THREADS / 64) {
+			const int y = b.y0 + r;
+			const bool yin = (unsigned)y < (unsigned)p.H;
+			const int64_t row = (int64_t)(p.H - 1 - y) * p.W;
+			for (int i = lane; i < w; i += 64) {
+				const int x = b.x0 + i;
+				stage[r * b.pitch + i] = yin && (unsigned)x < (unsigned)p.W ? plane[row + x] : (uint16_t)0;
+			}
+		}
+	}
+	__syncthreads();
+	const int x = tx0 + lane;
+	if (x >= p.oW)
+		return;
+	uint16_t *oplane = p.out + (int64_t)e.slot * p.opitch + (int64_t)c * p.out_plane;
+	const SgWarpGlobalSrc gsrc = {plane, p.W, p.H};
+	const SgWarpLdsSrc lsrc = {stage, b.x0, b.y0, b.pitch};
+	unsigned int stray = 0;
+	for (int yd = ty0 + wave; yd <= ty1; yd += SGW_THREADS / 64) {
+		const sgw_coord cd = sgw_coords<K>(M, p.bw, x, yd);
+		uint16_t v = 0;
+		if (!sgw_all_outside<K>(cd, p.W, p.H)) {
+			const float *wt = K > 1 ? p.tab + (size_t)cd.tab * K * K : nullptr;
+			if (lds && sgw_in_box<K>(cd, b)) {
+				v = sgw_pixel<K>(lsrc, cd, wt, p.W, p.H);
+			} else {
+				stray += lds;
+				v = sgw_pixel<K>(gsrc, cd, wt, p.W, p.H);
+			}
+		}
+		oplane[(int64_t)(p.oH - 1 - yd) * p.oW + x] = v;
+	}
+	if (stray)
+		atomicAdd(&ctr[2], (unsigned long long)stray);
+}
+
+/* the last call's span, once its launches have finished */
+static int sgw_fold(sg_ctx *ctx, SgDevice &dv) {
+	if (!dv.warp_pending)
+		return SG_OK;
+	HIPCHK(hipEventSynchronize(dv.warp_ev[1]));
+	float ms = 0.f;
+	HIPCHK(hipEventElapsedTime(&ms, dv.warp_ev[0], dv.warp_ev[1]));
+	dv.warp_ms += ms;
+	dv.warp_pending = false;
+	return SG_OK;
+}
+
+/* first: the call's first (or only) batch, which clears the counters and the span */
+static int sgw_run(sg_ctx *ctx, int dev_index, const SgWarpPlan &pl, const std::vector<SgWarpEntry> &table, const uint16_t *d_in,
+		uint16_t *d_out, void *stream, bool first) {
+	SgDevice &dv = ctx->dev[dev_index];
+	HIPCHK(hipSetDevice(dv.id));
+	hipStream_t s = sg_stream(dv, stream);
+	for (int k = 0; k < 2; k++)
+		if (!dv.warp_ev[k])
+			HIPCHK(hipEventCreate(&dv.warp_ev[k]));
+	int rc = sgw_fold(ctx, dv);
+	if (rc != SG_OK)
+		return rc;
+	/* a host call's later batches are no larger than its first: the counters stay where they are */
+	HIPCHK(ensure(dv.warp_work, pl.work_bytes));
+	if (first) {
+		dv.warp_ms = 0.;
+		dv.warp_launches = 0;
+		HIPCHK(hipMemsetAsync(dv.warp_work.p, 0, SGW_CTR_BYTES, s));
+	}
+	if (pl.interp != SG_WARP_NEAREST && dv.warp_tab_interp != pl.interp) {
+		std::vector<float> tab;
+		sg_tab2d(pl.interp, tab);
+		HIPCHK(ensure(dv.warp_tab, tab.size() * sizeof(float)));
+		HIPCHK(hipMemcpyAsync(dv.warp_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, s));
+		HIPCHK(hipStreamSynchronize(s));
+		dv.warp_tab_interp = pl.interp;
+	}
+	char *wk = (char *)dv.warp_work.p;
+	/* the previous call was folded above, so nothing reads the host copy any more */
+	const unsigned char *tb = (const unsigned char *)table.data();
+	dv.warp_table_h.assign(tb, tb + pl.table_bytes);
+	HIPCHK(hipMemcpyAsync(wk + pl.table_offset, dv.warp_table_h.data(), pl.table_bytes, hipMemcpyHostToDevice, s));
+	SgWarpSeq p;
+	p.in = d_in;
+	p.out = d_out;
+	p.W = pl.W;
+	p.H = pl.H;
+	p.C = pl.C;
+	p.oW = pl.oW;
+	p.oH = pl.oH;
+	p.in_plane = (int64_t)pl.W * pl.H;
+	p.out_plane = (int64_t)pl.oW * pl.oH;
+	p.fpitch = pl.frame_pitch;
+	p.opitch = pl.out_frame_pitch;
+	p.bw = pl.bw;
+	p.force_gather = pl.force_gather;
+	p.lds_samples = pl.lds_samples;
+	p.tab = pl.interp != SG_WARP_NEAREST ? (const float *)dv.warp_tab.p : nullptr;
+	p.table = (const SgWarpEntry *)(wk + pl.table_offset);
+	p.ctr = (unsigned long long *)wk;
+	HIPCHK(hipEventRecord(dv.warp_ev[0], s));
+	const size_t in_bytes = (size_t)pl.C * p.in_plane * sizeof(uint16_t);
+	for (int f = 0; f < pl.nframes; f++)
+		if (table[(size_t)f].action == SG_WARP_COPY)
+			HIPCHK(hipMemcpyAsync(d_out + (int64_t)table[(size_t)f].slot * pl.out_frame_pitch, d_in + (int64_t)f * pl.frame_pitch,
+					in_bytes, hipMemcpyDeviceToDevice, s));
+	for (int f0 = 0; f0 < pl.nframes; f0 += pl.frames_per_launch) {
+		const int nf = std::min(pl.frames_per_launch, pl.nframes - f0);
+		bool any = false;
+		for (int f = f0; f < f0 + nf; f++)
+			any = any || table[(size_t)f].action == SG_WARP_APPLY;
+		if (!any)
+			continue;
+		p.f0 = f0;
+		const dim3 grid((unsigned)pl.tiles_x, (unsigned)pl.tiles_y, (unsigned)(nf * pl.C));
+		switch (pl.K) {
+		case 1:
+			hipLaunchKernelGGL(k_warp_seq<1>, grid, dim3(SGW_THREADS), 0, s, p);
+			break;
+		case 2:
+			hipLaunchKernelGGL(k_warp_seq<2>, grid, dim3(SGW_THREADS), 0, s, p);
+			break;
+		case 4:
+			hipLaunchKernelGGL(k_warp_seq<4>, grid, dim3(SGW_THREADS), 0, s, p);
+			break;
+		default:
+			hipLaunchKernelGGL(k_warp_seq<8>, grid, dim3(SGW_THREADS), 0, s, p);
+		}
+		HIPCHK(hipGetLastError());
+		dv.warp_launches++;
+	}
+	HIPCHK(hipEventRecord(dv.warp_ev[1], s));
+	dv.warp_pending = true;
+	if (!stream)
+		HIPCHK(hipStreamSynchronize(s));
+	return SG_OK;
+}
+
+extern "C" int sg_warp_frames_u16_device(sg_ctx *ctx, int dev_index, const sg_warp_seq_desc *desc, const uint16_t *d_in,
+		int nframes, const double *hom, const int *action, const int *out_slot, uint16_t *d_out, void *stream) {
+	if (!sg_dev_ok(ctx, dev_index))
+		return SG_ERR_GENERIC;
+	SgWarpPlan pl;
+	std::vector<SgWarpEntry> table;
+	const int rc = sg_warp_plan(desc, nframes, hom, action, out_slot, d_in, d_out, ctx->knobs.warp_route, pl, table);
+	if (rc != SG_OK)
+		return set_err(ctx, rc, "%s", pl.err);
+	return sgw_run(ctx, dev_index, pl, table, d_in, d_out, stream, true);
+}
+
+/* host sequences: the source frames are staged in batches (SgHostBatches: frame_elems the source
+ * frame, tail_elems the output frame), each batch warped as a sequence of its own into device slots
+ * 0, 1, ... in frame order, and the written frames copied to out + out_slot * out_frame_pitch.  The
+ * span, launches and counters of sg_warp_frames_last_times are summed over the batches. */
+extern "C" int sg_warp_frames_u16(sg_ctx *ctx, const sg_warp_seq_desc *desc, const uint16_t *in, int nframes,
+		const double *hom, const int *action, const int *out_slot, uint16_t *out) {
+	if (!ctx || ctx->dev.empty())
+		return SG_ERR_GENERIC;
+	SgWarpPlan pl;
+	std::vector<SgWarpEntry> table;
+	int rc = sg_warp_plan(desc, nframes, hom, action, out_slot, in, out, ctx->knobs.warp_route, pl, table);
+	if (rc != SG_OK)
+		return set_err(ctx, rc, "%s", pl.err);
+	const size_t in_elems = (size_t)pl.C * pl.W * pl.H, out_elems = (size_t)pl.C * pl.oW * pl.oH;
+	SgHostBatches hb(ctx);
+	HIPCHK(hb.begin(nframes, in_elems, SG_HOST_BUDGET_1G, 0, 0, out_elems));
+	sg_warp_seq_desc bd = *desc;
+	bd.frame_pitch = bd.out_frame_pitch = 0;
+	std::vector<int> act((size_t)hb.batch), loc((size_t)hb.batch);
+	bool first = true;
+	while (hb.next()) {
+		const int f0 = hb.f0, nf = hb.nf;
+		int nw = 0;
+		for (int k = 0; k < nf; k++) {
+			act[(size_t)k] = table[(size_t)(f0 + k)].action;
+			loc[(size_t)k] = act[(size_t)k] == SG_WARP_SKIP ? -1 : nw++;
+		}
+		if (nw == 0 && !first)
+			continue;
+		if ((size_t)pl.frame_pitch == in_elems) {
+			HIPCHK(hb.upload(in));
+		} else {
+			for (int k = 0; k < nf; k++)
+				if (act[(size_t)k] != SG_WARP_SKIP)
+					HIPCHK(hipMemcpyAsync(hb.d + (size_t)k * in_elems, in + (int64_t)(f0 + k) * pl.frame_pitch,
+							in_elems * sizeof(uint16_t), hipMemcpyHostToDevice, hb.dv.stream));
+		}
+		SgWarpPlan bp;
+		std::vector<SgWarpEntry> bt;
+		rc = sg_warp_plan(&bd, nf, hom + (size_t)f0 * 9, act.data(), loc.data(), hb.d, hb.tail, ctx->knobs.warp_route, bp, bt);
+		if (rc != SG_OK)
+			return set_err(ctx, rc, "%s", bp.err);
+		rc = sgw_run(ctx, 0, bp, bt, hb.d, hb.tail, nullptr, first);
+		if (rc != SG_OK)
+			return rc;
+		first = false;
+		for (int k = 0; k < nf; k++)
+			if (loc[(size_t)k] >= 0)
+				HIPCHK(hipMemcpyAsync(out + (int64_t)table[(size_t)(f0 + k)].slot * pl.out_frame_pitch,
+						hb.tail + (size_t)loc[(size_t)k] * out_elems, out_elems * sizeof(uint16_t), hipMemcpyDeviceToHost,
+						hb.dv.stream));
+		HIPCHK(hipStreamSynchronize(hb.dv.stream));
+		rc = sgw_fold(ctx, hb.dv);
+		if (rc != SG_OK)
+			return rc;
+	}
+	return SG_OK;
+}
+
+extern "C" int sg_warp_frames_last_times(sg_ctx *ctx, int dev_index, double *ms, int *launches, uint64_t *tiles_lds,
+		uint64_t *tiles_gather, uint64_t *pixels_stray) {
+	if (!sg_dev_ok(ctx, dev_index))
+		return SG_ERR_GENERIC;
+	SgDevice &dv = ctx->dev[dev_index];
+	HIPCHK(hipSetDevice(dv.id));
+	const int rc = sgw_fold(ctx, dv);
+	if (rc != SG_OK)
+		return rc;
+	unsigned long long ctr[3] = {0, 0, 0};
+	if (dv.warp_work.p) {
+		std::vector<unsigned long long> sh((size_t)SGW_CTR_SHARDS * SGW_CTR_STRIDE);
+		HIPCHK(hipMemcpy(sh.data(), dv.warp_work.p, SGW_CTR_BYTES, hipMemcpyDeviceToHost));
+		for (int i = 0; i < SGW_CTR_SHARDS; i++)
+			for (int k = 0; k < 3; k++)
+				ctr[k] += sh[(size_t)i * SGW_CTR_STRIDE + k];
+	}
+	if (ms)
+		*ms = dv.warp_ms;
+	if (launches)
+		*launches = dv.warp_launches;
+	if (tiles_lds)
+		*tiles_lds = ctr[0];
+	if (tiles_gather)
+		*tiles_gather = ctr[1];
+	if (pixels_stray)
+		*pixels_stray = ctr[2];
+	return SG_OK;
+}

@@ -143,6 +143,16 @@ class CosmeFrame(ctypes.Structure):
                 ("ihot", ctypes.c_int64), ("bkg", ctypes.c_double * 3), ("avg_dev", ctypes.c_double * 3)]
 
 
+class WarpSeqDesc(ctypes.Structure):
+    """sg_warp_seq_desc: the shapes of a sequence warp"""
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("nb_layers", ctypes.c_int),
+                ("out_width", ctypes.c_int), ("out_height", ctypes.c_int), ("interpolation", ctypes.c_int),
+                ("frame_pitch", ctypes.c_int64), ("out_frame_pitch", ctypes.c_int64)]
+
+
+WARP_SKIP, WARP_APPLY, WARP_COPY = 0, 1, 2
+
+
 # every symbol include/sirilgpu.h and include/sirilgpu_io.h declare
 EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_u16_device",
            "sg_stack_u16_device_async", "sg_stack_collect", "sg_stack_wait_tail", "sg_device_count",
@@ -157,7 +167,8 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_prepro_frames", "sg_prepro_noise_device", "sg_findstar_device", "sg_findstar",
            "sg_findstar_fit_device", "sg_findstar_fit", "sg_register_ecc_u16_device", "sg_register_ecc_u16",
            "sg_register_ecc_last_times", "sg_cosme_autodetect_device", "sg_cosme_autodetect", "sg_cosme_last_times",
-           "sg_quality_u16_device", "sg_quality_u16", "sg_quality_last_times", "sg_quality_normalize", "sg_quality_select"]
+           "sg_quality_u16_device", "sg_quality_u16", "sg_quality_last_times", "sg_quality_normalize", "sg_quality_select",
+           "sg_warp_frames_u16_device", "sg_warp_frames_u16", "sg_warp_frames_last_times"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -262,6 +273,14 @@ def load():
     lib.sg_warp_u16_device.argtypes = [P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, ctypes.c_int,
                                        ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int, P]
     lib.sg_warp_u16_device.restype = ctypes.c_int
+    lib.sg_warp_frames_u16_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(WarpSeqDesc), P, ctypes.c_int, P, P, P, P, P]
+    lib.sg_warp_frames_u16_device.restype = ctypes.c_int
+    lib.sg_warp_frames_u16.argtypes = [P, ctypes.POINTER(WarpSeqDesc), P, ctypes.c_int, P, P, P, P]
+    lib.sg_warp_frames_u16.restype = ctypes.c_int
+    lib.sg_warp_frames_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
+                                              ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                              ctypes.POINTER(ctypes.c_uint64)]
+    lib.sg_warp_frames_last_times.restype = ctypes.c_int
     lib.sg_prepro_create.argtypes = [P, ctypes.c_int, ctypes.POINTER(PreproDesc), ctypes.POINTER(P)]
     lib.sg_prepro_create.restype = ctypes.c_int
     lib.sg_prepro_free.argtypes = [P]
@@ -700,6 +719,61 @@ class Context:
         rc = self.lib.sg_warp_u16_device(self.ctx, dev_index, ctypes.c_void_p(d_in), W, H, C, ctypes.c_void_p(d_out),
                                          oW, oH, h, interpolation, ctypes.c_void_p(stream) if stream else None)
         self.check(rc, "sg_warp_u16_device")
+
+    @staticmethod
+    def _warp_seq_args(nframes, hom, action, out_slot):
+        h = np.ascontiguousarray(hom, dtype=np.float64).reshape(-1)
+        if h.size != 9 * max(nframes, 0):
+            raise ValueError("hom: one 3x3 homography per frame")
+        a = None if action is None else np.ascontiguousarray(action, dtype=np.int32)
+        s = None if out_slot is None else np.ascontiguousarray(out_slot, dtype=np.int32)
+        if (a is not None and a.size != nframes) or (s is not None and s.size != nframes):
+            raise ValueError("action / out_slot: one entry per frame")
+        return h, a, s
+
+    def warp_frames_device(self, d_in, nframes, W, H, C, d_out, oW, oH, hom, interpolation, action=None, out_slot=None,
+                           frame_pitch=0, out_frame_pitch=0, stream=None, dev_index=0):
+        """cvTransformImage on every frame of a resident sequence, one homography each (sg_warp_frames_u16_device):
+        frame f = C planes of W x H at d_in + f * frame_pitch elements (0 = tight), hom [nframes][3][3]; action[f]
+        WARP_SKIP / WARP_APPLY / WARP_COPY (None = all APPLY); the result goes to output frame out_slot[f] (None = f)
+        at d_out + out_slot[f] * out_frame_pitch elements.  Returns rc; with a stream, once the work is queued on it."""
+        h, a, s = self._warp_seq_args(nframes, hom, action, out_slot)
+        d = WarpSeqDesc(W, H, C, oW, oH, interpolation, frame_pitch, out_frame_pitch)
+        P = ctypes.c_void_p
+        return self.lib.sg_warp_frames_u16_device(self.ctx, dev_index, ctypes.byref(d), P(d_in), nframes, h.ctypes.data_as(P),
+                                                  a.ctypes.data_as(P) if a is not None else None,
+                                                  s.ctypes.data_as(P) if s is not None else None, P(d_out),
+                                                  P(stream) if stream else None)
+
+    def warp_frames(self, frames, hom, out_size=None, interpolation=OPENCV_LINEAR, action=None, out_slot=None, out=None):
+        """the same on host frames [N][C][H][W] (sg_warp_frames_u16).  Returns (rc, out): out [slots][C][oH][oW], a new
+        zero array with a slot per frame unless one is passed in (u16, C-contiguous); only written frames are touched."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        N, C, H, W = frames.shape
+        oW, oH = out_size if out_size else (W, H)
+        h, a, s = self._warp_seq_args(N, hom, action, out_slot)
+        if out is None:
+            out = np.zeros((N, C, oH, oW), dtype=np.uint16)
+        if out.dtype != np.uint16 or not out.flags.c_contiguous or out.shape[1:] != (C, oH, oW):
+            raise ValueError("out: a C-contiguous u16 array [slots][C][oH][oW]")
+        written = [f if s is None else int(s[f]) for f in range(N) if a is None or a[f] != WARP_SKIP]
+        if written and max(written) >= out.shape[0]:
+            raise ValueError("out: fewer frames than the largest slot")
+        d = WarpSeqDesc(W, H, C, oW, oH, interpolation, 0, 0)
+        P = ctypes.c_void_p
+        rc = self.lib.sg_warp_frames_u16(self.ctx, ctypes.byref(d), frames.ctypes.data_as(P), N, h.ctypes.data_as(P),
+                                         a.ctypes.data_as(P) if a is not None else None,
+                                         s.ctypes.data_as(P) if s is not None else None, out.ctypes.data_as(P))
+        return rc, out
+
+    def warp_frames_last_times(self, dev_index=0):
+        """(device ms, kernel launches, tiles_lds, tiles_gather, pixels_stray) of the last sequence warp on that device,
+        after waiting for it"""
+        ms, n = ctypes.c_double(), ctypes.c_int()
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self.check(self.lib.sg_warp_frames_last_times(self.ctx, dev_index, ctypes.byref(ms), ctypes.byref(n), ctypes.byref(a),
+                                                      ctypes.byref(b), ctypes.byref(c)), "sg_warp_frames_last_times")
+        return ms.value, n.value, a.value, b.value, c.value
 
     def stack_seq(self, desc, seq):
         """Host-pull stack whose pull callback is the library's own sg_seq_read_region (C),
