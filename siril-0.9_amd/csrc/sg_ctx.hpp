@@ -164,26 +164,17 @@ struct SgKnobs {
 	int hist_sigmedian = 1;		/* SG_HIST_SIGMEDIAN: 0 = SIGMEDIAN on the sorted kernel only (A/B) */
 	int pull_overlap = 1;		/* SG_PULL_OVERLAP: 0 = host-pull bands read and stacked one after the other (A/B) */
 	int qsub_threads = 64;		/* SG_QSUB_THREADS: 64 measured best (scripts/gpu_qsub.sh) */
-	int qgrad_threads = 128;	/* SG_QGRAD_THREADS: 128 measured best (scripts/gpu_qgrad.sh) */
 	int reg_batch = 0;		/* SG_REG_BATCH: pairs per launch (0 = up to 2 GB of pair planes) */
 	int reg_cw = 0;			/* SG_REG_CW: columns per column-pass workgroup (0 = 8192 / S) */
 	int reg_path = 2;		/* SG_REG_PATH: 2 = half-spectrum passes (power-of-two sides), 3 = the generic passes */
-	int reg_xcd = 1;		/* SG_REG_XCD: 0 = column strips in dispatch order */
-	int reg_pb = 1;			/* SG_REG_PB: pairs per strip block of the fused column pass (1 = pair-major) */
 	int reg_fp = 32;		/* SG_REG_FP: 32 = fp32 half-spectrum passes, near ties re-run in fp64; 64 = fp64 only */
 	int reg_cw32 = 4;		/* SG_REG_CW32: columns per strip of the fp32 column pass (4: 32-B row segments, no spill; 8: 64-B segments, 16 elements per thread) */
-	int reg_colocc = 1;		/* SG_REG_COLOCC: 1 = fp32 column pass held to 64 VGPRs (two 1024-thread workgroups per CU: registration 6.86 -> 6.21 ms on configs[1], profiles/r03t_ab_reg_cols.log), 0 = 76 VGPRs, one workgroup */
 	int reg_wcol = 1;		/* SG_REG_WCOL: 1 = wave-level fp32 column pass at S = 2048 (k_reg_cols_xpower_w), 0 = block-level */
 	int reg_genfuse = 1;		/* SG_REG_GENFUSE: 1 = generic sides' fused column pass (k_gen_cols_xpower), 0 = rows + k_gen_xpower + rows */
 	int reg_rpw = 8;		/* SG_REG_RPW: rows per wave of the wave-level forward row pass (the next row fetched during this one's transform) */
-	int reg_qafter = 0;		/* SG_REG_QAFTER: 1 = the quality estimate queued after the first batch's forward rows (beside the column pass) */
 	int reg_qfold = 12;		/* SG_REG_QFOLD = r (3, 6, 9 ...): QualityEstimate's 3x3 subsample folded into the wave-level forward row pass, r consecutive rows per wave (S = 2048, fp32; configs[1] registration 3.10 -> 2.95 ms, r = 6-12 equal, 24 / 48 slower, profiles/r06s_*, r06t_*); 0 = k_quality_sub */
 	int linfit_waves = 8;		/* SG_LINFIT_WAVES: waves per 64-pixel k_stack_linfit tile (4, 8 or 16 (KM = 8)) */
 	int linfit_fast = 1;		/* SG_LINFIT_FAST: 1 = LINEARFIT through the decision-exact k_stack_linfit (16 <= N <= 1024), redo pixels to the sorted kernel; 0 = every pixel through the sorted kernel */
-	int qgrad_stream = 1;		/* SG_QGRAD_STREAM: 1 = the quality gradient streamed down 60-column bands (k_quality_grad_s), 0 = tiled */
-	int reg_wcolw = 8;		/* SG_REG_WCOLW: columns per strip of the wave-level column pass (8: 64-B row segments, one workgroup per CU: configs[1] registration 3.33 -> 3.20 ms and the pass's HBM writes 1.57x -> 1.0x the plane, profiles/r05w_*; 4: 32-B segments, two workgroups per CU) */
-	int reg_specp = 1;		/* SG_REG_SPECP: 1 = the wave-level column pass reads the reference spectrum in lane order (k_spec_perm), 0 = through LDS */
-	int reg_refconc = 1;		/* SG_REG_REFCONC: 1 = fp32 reference spectrum on its own stream beside the first batch's forward rows */
 	int norm_fma = 2;		/* SG_NORM_FMA: normalised histogram stacks load with one fma per sample (1, 2) or, additive with
 					 * scale 1, an integer offset (2) when a device check (k_norm_fma_check) finds that equal to the
 					 * reference's roundings for every u16 value of every frame; 0 = the reference's operations */
@@ -213,35 +204,25 @@ struct SgKnobs {
 			host_budget = atoll(e) > 0 ? atoll(e) : 0;
 		const int qs = sg_env_int("SG_QSUB_THREADS", 64, 1024, 64);
 		qsub_threads = qs % 64 == 0 ? qs : 64;
-		const int qg = sg_env_int("SG_QGRAD_THREADS", 64, 256, 128);
-		qgrad_threads = (qg == 64 || qg == 128 || qg == 256) ? qg : 128;
 		reg_batch = sg_env_int("SG_REG_BATCH", 1, 1024, 0);
 		reg_cw = sg_env_int("SG_REG_CW", 1, 64, 0);
 		while (reg_cw & (reg_cw - 1))	/* strips of a power of two columns (the FFT helpers split indices by shifts) */
 			reg_cw &= reg_cw - 1;
 		reg_path = sg_env_int("SG_REG_PATH", 2, 3, 2);
-		reg_xcd = sg_env_int("SG_REG_XCD", 0, 1, 1);
-		reg_pb = sg_env_int("SG_REG_PB", 1, 64, 1);
 		reg_fp = sg_env_int("SG_REG_FP", 32, 64, 32) == 64 ? 64 : 32;
 		reg_genfuse = sg_env_int("SG_REG_GENFUSE", 0, 1, 1);
 		reg_wcol = sg_env_int("SG_REG_WCOL", 0, 1, 1);
 		reg_cw32 = sg_env_int("SG_REG_CW32", 1, 16, 4);
 		while (reg_cw32 & (reg_cw32 - 1))
 			reg_cw32 &= reg_cw32 - 1;
-		reg_colocc = sg_env_int("SG_REG_COLOCC", 0, 1, 1);
 		reg_rpb = sg_env_int("SG_REG_RPB", 1, 64, 4);
 		cosme_chunk = sg_env_int("SG_COSME_CHUNK", 1, 65535, 0);
 		cosme_list = sg_env_int("SG_COSME_LIST", 1, 1 << 30, 0);
 		quality_route = sg_env_int("SG_QUALITY_ROUTE", 0, 2, 0);
 		quality_chunk = sg_env_int("SG_QUALITY_CHUNK", 1, 65535, 0);
 		quality_lds = sg_env_int("SG_QUALITY_LDS", 64, 160 * 1024, 0);
-		reg_refconc = sg_env_int("SG_REG_REFCONC", 0, 1, 1);
-		reg_specp = sg_env_int("SG_REG_SPECP", 0, 1, 1);
-		reg_wcolw = sg_env_int("SG_REG_WCOLW", 4, 8, 8) == 8 ? 8 : 4;
-		qgrad_stream = sg_env_int("SG_QGRAD_STREAM", 0, 1, 1);
 		linfit_fast = sg_env_int("SG_LINFIT_FAST", 0, 1, 1);
 		linfit_waves = sg_env_int("SG_LINFIT_WAVES", 4, 16, 8);
-		reg_qafter = sg_env_int("SG_REG_QAFTER", 0, 1, 0);
 		reg_rpw = sg_env_int("SG_REG_RPW", 1, 64, 8);
 		reg_qfold = sg_env_int("SG_REG_QFOLD", 0, 63, 12) / 3 * 3;
 		norm_fma = sg_env_int("SG_NORM_FMA", 0, 2, 2);

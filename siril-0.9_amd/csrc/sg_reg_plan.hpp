@@ -172,17 +172,13 @@ enum SgRegRoute {
 };
 /* the fused fp32 column pass (forward columns, cross power, inverse columns) */
 enum SgRegCols32 {
-	SG_COLS32_BLOCK8 = 0,		/* k_reg_cols_xpower<float2, 8> */
-	SG_COLS32_BLOCK8_OCC,		/* k_reg_cols_xpower<float2, 8, 8>: 64 VGPRs (8 waves / SIMD, two 1024-thread workgroups per CU) */
+	SG_COLS32_BLOCK8_OCC = 0,	/* k_reg_cols_xpower<float2, 8, 8>: 64 VGPRs (8 waves / SIMD, two 1024-thread workgroups per CU) */
 	SG_COLS32_BLOCK16,		/* k_reg_cols_xpower<float2, 16>: 16 elements per thread */
-	SG_COLS32_WAVE4_PERM,		/* k_reg_cols_xpower_w<true, 4>: the reference spectrum in lane order */
-	SG_COLS32_WAVE8_PERM,		/* k_reg_cols_xpower_w<true, 8>: 8-column strips, 64-B row segments, one workgroup per CU */
-	SG_COLS32_WAVE4_LDS		/* k_reg_cols_xpower_w<false, 4>: the reference spectrum through LDS */
+	SG_COLS32_WAVE8_PERM		/* k_reg_cols_xpower_w: 8-column strips, 64-B row segments, one workgroup per CU, the reference spectrum in lane order */
 };
 /* when the quality estimate is queued */
 enum SgRegQRoute {
 	SG_REG_Q_FOLDED = 0,	/* the subsample inside the wave-level forward rows, the gradient behind the last batch's */
-	SG_REG_Q_DEFERRED,	/* SG_REG_QAFTER: behind the first batch's forward rows */
 	SG_REG_Q_UPFRONT	/* ahead of the reference spectrum */
 };
 /* the kernels with dynamic LDS */
@@ -199,8 +195,8 @@ enum SgRegKernel {
 	SG_RK_INV32,			/* k_reg_rows_inv_half_argmax<float2, false> */
 	SG_RK_COLS32_8,			/* + (ept32 == 16): k_reg_cols<float2, 8 / 16> */
 	SG_RK_COLS32_16,
-	SG_RK_XPOWER32,			/* + SgRegCols32: the six instances of the fused column pass */
-	SG_RK_XPOWER32_END = SG_RK_XPOWER32 + 6,
+	SG_RK_XPOWER32,			/* + SgRegCols32: the three instances of the fused column pass */
+	SG_RK_XPOWER32_END = SG_RK_XPOWER32 + 3,
 	SG_RK_FWD_PERM_W = SG_RK_XPOWER32_END,	/* k_reg_cols_fwd_perm_w */
 	SG_RK_FWD_W,			/* + folded: k_reg_rows_fwd_half_w<false / true> */
 	SG_RK_FWD_W_FOLD,
@@ -242,8 +238,7 @@ struct SgRegPlan {
 	/* knob-derived switches */
 	int cols32;			/* SgRegCols32 */
 	int qroute, qfold;		/* SgRegQRoute; rows per wave of the folded subsample (0: not folded) */
-	bool specp_on, ref_conc;
-	int xcdmap, pb;
+	bool specp_on;			/* the fp32 reference spectrum also in the wave-level column pass's lane order */
 	/* byte layouts: reg_tw in doubles (tw, then for Bluestein twm, the chirp, bhat) */
 	size_t n_tw, n_twm, n_ch, n_bh, tab_total;
 	size_t spec_bytes, work_bytes;
@@ -353,21 +348,16 @@ static void sg_reg_plan_half(const SgKnobs &k, SgRegPlan &pl) {
 	while (rpb > 1 && S % rpb != 0)
 		rpb >>= 1;
 	pl.rpb = rpb;
-	/* wave-level column pass: the fp32 reference spectrum also in its lane order (k_spec_perm,
-	 * SG_REG_SPECP=0: staged through LDS, A/B) */
-	pl.specp_on = pl.fp32 && pl.wcol && k.reg_specp;
-	pl.cols32 = pl.wcol && pl.specp_on && k.reg_wcolw == 8 ? SG_COLS32_WAVE8_PERM :
-		pl.wcol && pl.specp_on ? SG_COLS32_WAVE4_PERM : pl.wcol ? SG_COLS32_WAVE4_LDS :
-		pl.ept32 == 16 ? SG_COLS32_BLOCK16 : k.reg_colocc ? SG_COLS32_BLOCK8_OCC : SG_COLS32_BLOCK8;
+	/* wave-level column pass: the fp32 reference spectrum also in its lane order (k_reg_cols_fwd_perm_w) */
+	pl.specp_on = pl.fp32 && pl.wcol;
+	pl.cols32 = pl.wcol ? SG_COLS32_WAVE8_PERM : pl.ept32 == 16 ? SG_COLS32_BLOCK16 : SG_COLS32_BLOCK8_OCC;
 	const int row = (int)pl.row_lds, row32 = (int)pl.row_lds32, col = (int)pl.colh_lds, col32 = (int)pl.colh_lds32,
 		  w = (int)pl.wcol_lds;
 	pl.lds_attrs = {{SG_RK_COLS64, col}, {SG_RK_FWD64, row}, {SG_RK_INV64, row}, {SG_RK_INV64_CAND, row},
 		{SG_RK_XPOWER64, col}, {SG_RK_FWD32, row32}, {SG_RK_INV32, row32}, {SG_RK_COLS32_8, col32},
-		{SG_RK_COLS32_16, col32}, {SG_RK_XPOWER32 + SG_COLS32_BLOCK8, col32},
-		{SG_RK_XPOWER32 + SG_COLS32_BLOCK8_OCC, col32}, {SG_RK_XPOWER32 + SG_COLS32_BLOCK16, col32},
-		{SG_RK_XPOWER32 + SG_COLS32_WAVE4_PERM, w}, {SG_RK_XPOWER32 + SG_COLS32_WAVE8_PERM, 2 * w},
-		{SG_RK_XPOWER32 + SG_COLS32_WAVE4_LDS, w}, {SG_RK_FWD_PERM_W, w}, {SG_RK_FWD_W, w}, {SG_RK_FWD_W_FOLD, w},
-		{SG_RK_INV_W, w}};
+		{SG_RK_COLS32_16, col32}, {SG_RK_XPOWER32 + SG_COLS32_BLOCK8_OCC, col32},
+		{SG_RK_XPOWER32 + SG_COLS32_BLOCK16, col32}, {SG_RK_XPOWER32 + SG_COLS32_WAVE8_PERM, 2 * w},
+		{SG_RK_FWD_PERM_W, w}, {SG_RK_FWD_W, w}, {SG_RK_FWD_W_FOLD, w}, {SG_RK_INV_W, w}};
 }
 
 /* pairs per launch and the quality route */
@@ -390,13 +380,11 @@ static void sg_reg_plan_batches(const SgKnobs &k, SgRegPlan &pl) {
 	pl.Bc = B > 1 ? B : 1;
 	/* fp64 re-runs of near ties in the same work buffer */
 	pl.B64 = pl.fp32 ? (int)std::max<size_t>(1, (size_t)pl.Bc * pl.pair_bytes / (pl.plane * SG_REG_SIZEOF_C64)) : pl.Bc;
-	pl.ref_conc = pl.fp32 && k.reg_refconc;	/* A/B knob SG_REG_REFCONC */
 	/* SG_REG_QFOLD (A/B): the quality estimate's subsample from the wave-level forward rows (every
 	 * frame of qframes passes through them: the reference and each pair), then only the gradient
 	 * kernel on the aux stream behind the last batch's forward rows */
 	pl.qfold = (pl.specp_on && pl.npairs_total > 0 && S == 2048) ? k.reg_qfold : 0;
-	pl.qroute = pl.qfold ? SG_REG_Q_FOLDED :
-		(pl.fp32 && pl.npairs_total > 0 && k.reg_qafter) ? SG_REG_Q_DEFERRED : SG_REG_Q_UPFRONT;
+	pl.qroute = pl.qfold ? SG_REG_Q_FOLDED : SG_REG_Q_UPFRONT;
 	pl.tol_main = pl.fp32 ? -15 : -32;
 }
 
@@ -455,8 +443,6 @@ static int sg_reg_plan(int nframes, int S, int ref_image, const int *included, i
 	pl.logS = ilog2(S);
 	pl.plane = (size_t)S * S;
 	pl.tgrid = (unsigned)((S + 31) / 32);
-	pl.xcdmap = k.reg_xcd;	/* A/B knob SG_REG_XCD: 0 = strips in dispatch order */
-	pl.pb = k.reg_pb;
 	sg_reg_plan_frames(included, pl);
 	/* power-of-two sides take the half-spectrum passes; any other side the generic mixed-radix /
 	 * Bluestein passes (SG_REG_PATH=3 forces those for a power of two, A/B; the round-1/2 full-

@@ -41,8 +41,8 @@
  * XCDs, so neighbouring strips (which share 128-B lines: a strip row is 64 B) would be
  * fetched by two L2s; give each XCD a contiguous range of strips instead (PMC FETCH_SIZE
  * of the column passes halves) */
-__device__ __forceinline__ int sg_xcd_strip(int id, int n, int xcdmap) {
-	if (!xcdmap || (n & 7))
+__device__ __forceinline__ int sg_xcd_strip(int id, int n) {
+	if (n & 7)
 		return id;
 	return (id & 7) * (n >> 3) + (id >> 3);
 }
@@ -50,10 +50,10 @@ __device__ __forceinline__ int sg_xcd_strip(int id, int n, int xcdmap) {
 /* column pass (forward or inverse) over strips of CW adjacent columns */
 template <class C, int EPT = 8>
 __global__ void __launch_bounds__(1024)
-k_reg_cols(C *__restrict__ work, int S, int logS, int CW, const C *__restrict__ tw, int inverse, int xcdmap) {
+k_reg_cols(C *__restrict__ work, int S, int logS, int CW, const C *__restrict__ tw, int inverse) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	C *buf = (C *)smem;
-	const int x0 = sg_xcd_strip(blockIdx.x, gridDim.x, xcdmap) * CW, pair = blockIdx.y;
+	const int x0 = sg_xcd_strip(blockIdx.x, gridDim.x) * CW, pair = blockIdx.y;
 	const int bstride = sg_col_stride<C>(S);
 	C *base = work + (size_t)pair * S * S + x0;
 	(void)logS;
@@ -178,21 +178,10 @@ __device__ __forceinline__ C sg_rconj(C r, C f) {
 template <class C, int EPT = 8, int WPE = 1>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(WPE)))
 k_reg_cols_xpower(C *__restrict__ work, const C *__restrict__ spec, int S, int CW,
-		const C *__restrict__ tw, int xcdmap, int pb) {
+		const C *__restrict__ tw) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	C *buf = (C *)smem;
-	int x0 = sg_xcd_strip(blockIdx.x, gridDim.x, xcdmap) * CW, pair = blockIdx.y;
-	/* pb > 1: blocks of pb pairs per strip dispatched back to back on one XCD (strip-major
-	 * inside a pair block), so the strip's reference-spectrum columns are read from HBM once per
-	 * block and from that XCD's L2 by the block's other pairs, while neighbouring strips of one
-	 * pair still run close together (their 64-B rows share 128-B lines) */
-	const int ns = gridDim.x, np = gridDim.y;
-	if (pb > 1 && xcdmap && (ns & 7) == 0 && np % pb == 0) {
-		const int id = blockIdx.x + ns * blockIdx.y, xcd = id & 7, local = id >> 3, s8 = ns >> 3;
-		const int strip = xcd * s8 + (local / pb) % s8;
-		pair = (local / (pb * s8)) * pb + local % pb;
-		x0 = strip * CW;
-	}
+	const int x0 = sg_xcd_strip(blockIdx.x, gridDim.x) * CW, pair = blockIdx.y;
 	typedef typename SgReal<C>::T T;
 	const int bstride = sg_col_stride<C>(S), H = S >> 1;
 	C *base = work + (size_t)pair * S * S + x0;
@@ -249,7 +238,7 @@ k_reg_cols_xpower(C *__restrict__ work, const C *__restrict__ spec, int S, int C
 
 /* ---------------------------------------------------------------------------------------
  * Wave-level fused column pass, fp32, S = 2048 (configs[1] / configs[4]): one WAVE per column
- * of a 4-column strip, the 2048-point transforms as 32 x 64 four-step FFTs held in registers
+ * of an 8-column strip, the 2048-point transforms as 32 x 64 four-step FFTs held in registers
  * (32 complex per lane), so the block synchronises only around the coalesced strip load and
  * store.  Forward: lane l holds x[64 j + l] (j = 0..31); a 32-point DFT over j in registers,
  * twiddles w_S^(l k1), a transpose through the wave's own LDS column (rows of 66 for banks) to
@@ -468,20 +457,19 @@ k_reg_cols_fwd_perm_w(float2 *__restrict__ spec, float2 *__restrict__ specp, con
 	}
 }
 
-template <bool PERM, int CW>
-__global__ void __launch_bounds__(64 * CW) __attribute__((amdgpu_waves_per_eu(SG_WCOL_WPE)))
+__global__ void __launch_bounds__(64 * 8) __attribute__((amdgpu_waves_per_eu(SG_WCOL_WPE)))
 k_reg_cols_xpower_w(float2 *__restrict__ work, const float2 *__restrict__ spec, const float2 *__restrict__ specp,
-		const float2 *__restrict__ tw, int xcdmap) {
-	constexpr int S = 2048, H = 1024, P = 32, CS = SG_WCOL_CS, TR = 66;
+		const float2 *__restrict__ tw) {
+	constexpr int S = 2048, H = 1024, P = 32, CW = 8, CS = SG_WCOL_CS, TR = 66;
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 	float2 *lds = (float2 *)smem;
 	const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-	const int x0 = sg_xcd_strip(blockIdx.x, gridDim.x, xcdmap) * CW, pair = blockIdx.y;
+	const int x0 = sg_xcd_strip(blockIdx.x, gridDim.x) * CW, pair = blockIdx.y;
 	float2 *base = work + (size_t)pair * S * S + x0;
 	float2 *col = lds + wave * CS;
 	const int sw = sg_strip_row<CW>(0, wave);	/* sg_strip_row of this wave's column: lane ^ sw */
 	auto wsync = [] { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); };
-	/* strip -> LDS: rows of 4 columns (32 B), column c at lds + c CS */
+	/* strip -> LDS: rows of 8 columns (64 B), column c at lds + c CS */
 #pragma unroll
 	for (int it = 0; it < P; it++) {
 		const int r = threadIdx.x / CW + 64 * it, c = threadIdx.x % CW;
@@ -494,9 +482,9 @@ k_reg_cols_xpower_w(float2 *__restrict__ work, const float2 *__restrict__ spec, 
 		v[j] = col[64 * j + (lane ^ sw)];
 	const int km = lane >> 1, hm = lane & 1;
 	const int kx = (x0 + wave) & (H - 1);
-	/* PERM: the reference column's loads issued now, in flight during the forward transform */
+	/* the reference column's loads (specp: lane order) issued now, in flight during the forward transform */
 	float2 r[P];
-	if (PERM && kx) {
+	if (kx) {
 		const float2 *sp = specp + (size_t)kx * S;
 #pragma unroll
 		for (int k = 0; k < P; k++)
@@ -505,31 +493,12 @@ k_reg_cols_xpower_w(float2 *__restrict__ work, const float2 *__restrict__ spec, 
 	/* ---- forward ---- */
 	sg_fft2048_wave<false>(v, col, tw, lane);
 	/* ---- cross power at ky = km + 32 k + 1024 hm ---- */
-	/* PERM: the reference column from specp, in lane order.  Otherwise the reference spectrum's
-	 * strip through LDS (coalesced 32-B rows, as the work strip; read per lane at its ky it
-	 * touched 64 rows per instruction).  A packed column 0's wave keeps its LDS column for
-	 * Z(-ky) and reads its reference column directly. */
-	if (!PERM) {
-		__syncthreads();	/* every wave is done with its transposes */
-		const int kx0 = x0 & (H - 1);	/* a strip lies inside one half */
-#pragma unroll
-		for (int it = 0; it < P; it++) {
-			const int r = threadIdx.x / CW + 64 * it, c = threadIdx.x % CW;
-			if (kx0 + c)
-				lds[c * CS + r] = spec[(size_t)r * S + kx0 + c];
-		}
-		__syncthreads();
-	}
+	/* A packed column 0's wave keeps its LDS column for Z(-ky) and reads its reference column
+	 * from spec by ky. */
 	if (kx) {
-		if (PERM) {
 #pragma unroll
-			for (int k = 0; k < P; k++)
-				v[k] = sg_rconjf(r[k], v[k]);
-		} else {
-#pragma unroll
-			for (int k = 0; k < P; k++)
-				v[k] = sg_rconjf(col[km + 32 * k + 1024 * hm], v[k]);
-		}
+		for (int k = 0; k < P; k++)
+			v[k] = sg_rconjf(r[k], v[k]);
 	} else {	/* packed column: Z = F0 + i FN, the reference likewise; needs Z(-ky) */
 		wsync();
 #pragma unroll
@@ -937,7 +906,6 @@ k_reg_rows_inv_half_argmax(const C *__restrict__ work, int S, const C *__restric
  * ------------------------------------------------------------------------------------- */
 #define SG_Q_THRESHOLD (40 << 8)
 #define SG_QROWS 4	/* subsampled rows per k_quality_sub workgroup */
-#define SG_QGT 16	/* output rows per k_quality_grad tile (64 columns) */
 
 /* SubSample (:223-234) of one 3x3 sample row, plus the running max of the middle rows
  * (the maxp[] loop :119-133 reduces to max over 0 < v < 65530) */
@@ -1005,121 +973,16 @@ k_quality_sub(SgSel sel, int al, const int *__restrict__ qframes, int S, int xs,
 		atomicMax(qmax + q, m);
 }
 
-/* stretched sample (:139-148): v * (60000 / max), truncated, clamped at 65535 */
-__device__ __forceinline__ int sg_q_stretch(const uint16_t *b, int idx, double mult, bool stretch) {
-	unsigned int v = b[idx];
-	if (stretch) {
-		v = (unsigned int)((double)v * mult);
-		if (v > 65535u)
-			v = 65535u;
-	}
-	return (int)v;
-}
-
 /* _smooth_image_16 (:324-349) + Gradient (:236-321): threshold map dilated 3x3 inside the
- * 10 % margins, gradient energy over mapped pixels; exact integer sums */
-__global__ void __launch_bounds__(256)
-k_quality_grad(const uint16_t *__restrict__ qbuf, int xs, int ys, const unsigned int *__restrict__ qmax,
-		unsigned long long *__restrict__ acc /* [q][3]: val, pixels, thresholded */) {
-	__shared__ unsigned long long sv[4], sp[4], sc[4];
-	/* a 64 x SG_QGT tile of outputs: stretched samples of the 68 x (SG_QGT + 4)
-	 * neighbourhood, then the smoothed values of the 66 x (SG_QGT + 2) one, each formed once
-	 * in LDS; the blockDim.x / 64 waves take the output rows in turn */
-	__shared__ unsigned int st[SG_QGT + 4][68];
-	__shared__ int sms[SG_QGT + 2][66];
-	const int q = blockIdx.z;
-	const uint16_t *b = qbuf + (size_t)q * xs * ys;
-	const unsigned int mx = qmax[q];
-	const bool stretch = mx > 0;
-	const double mult = stretch ? (double)60000 / (double)mx : 1.0;
-	const int yb = (int)((double)ys * 0.1) + 1;
-	const int xb = (int)((double)xs * 0.1) + 1;
-	const int x0 = blockIdx.x * 64, y0 = blockIdx.y * SG_QGT;
-	for (int i = threadIdx.x; i < (SG_QGT + 4) * 68; i += blockDim.x) {
-		const int ly = i / 68, lx = i - ly * 68;
-		const int gx = x0 - 2 + lx, gy = y0 - 2 + ly;
-		st[ly][lx] = (gx >= 0 && gx < xs && gy >= 0 && gy < ys) ? (unsigned int)sg_q_stretch(b, gy * xs + gx, mult, stretch)
-									     : 0u;
-	}
-	__syncthreads();
-	for (int i = threadIdx.x; i < (SG_QGT + 2) * 66; i += blockDim.x) {
-		const int ly = i / 66, lx = i - ly * 66;
-		const int qx = x0 - 1 + lx, qy = y0 - 1 + ly;
-		int v = 0;
-		if (qx >= 1 && qx <= xs - 2 && qy >= 1 && qy <= ys - 2) {
-			unsigned int sum = 0;
-			for (int ey = 0; ey < 3; ey++)
-				for (int ex = 0; ex < 3; ex++)
-					sum += st[ly + ey][lx + ex];
-			v = (int)(sum / 9);
-		}
-		sms[ly][lx] = v;
-	}
-	__syncthreads();
-	const int tx = threadIdx.x & 63;
-	const int x = x0 + tx;
-	unsigned long long val = 0, pix = 0, cnt = 0;
-	for (int ty = threadIdx.x >> 6; ty < SG_QGT; ty += (int)(blockDim.x >> 6)) {
-	const int y = y0 + ty;
-	if (x >= xb && x < xs - xb && y >= yb && y < ys - yb) {
-		/* smoothed values on the 3x3 neighbourhood of (x, y) */
-		int sm[3][3];
-		for (int dy = 0; dy < 3; dy++)
-			for (int dx = 0; dx < 3; dx++)
-				sm[dy][dx] = sms[ty + dy][tx + dx];
-		if (sm[1][1] >= SG_Q_THRESHOLD)
-			cnt += 1;
-		bool mapped = false;
-		for (int dy = -1; dy <= 1; dy++)
-			for (int dx = -1; dx <= 1; dx++) {
-				const int qx = x + dx, qy = y + dy;
-				if (qx >= xb && qx < xs - xb && qy >= yb && qy < ys - yb &&
-						sm[dy + 1][dx + 1] >= SG_Q_THRESHOLD)
-					mapped = true;
-			}
-		if (mapped) {
-			const long long d1 = sm[1][1] - sm[1][2];
-			const long long d2 = sm[1][1] - sm[2][1];
-			val += (unsigned long long)(d1 * d1 + d2 * d2);
-			pix += 1;
-		}
-	}
-	}
-	for (int o = 32; o > 0; o >>= 1) {
-		val += __shfl_down(val, o, 64);
-		pix += __shfl_down(pix, o, 64);
-		cnt += __shfl_down(cnt, o, 64);
-	}
-	const int wave = threadIdx.x >> 6;
-	if ((threadIdx.x & 63) == 0) {
-		sv[wave] = val;
-		sp[wave] = pix;
-		sc[wave] = cnt;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		for (int w = 1; w < (int)(blockDim.x >> 6); w++) {
-			val += sv[w];
-			pix += sp[w];
-			cnt += sc[w];
-		}
-		if (val)
-			atomicAdd(acc + q * 3, val);
-		if (pix)
-			atomicAdd(acc + q * 3 + 1, pix);
-		if (cnt)
-			atomicAdd(acc + q * 3 + 2, cnt);
-	}
-}
-
-/* k_quality_grad streamed down a band: one wave per (60-column band, SG_QGS_ROWS output rows,
- * frame) of the 10 % margins' interior, lane l at column x0 - 2 + l.  Each input row is loaded
- * and stretched once (SG_QGS_PF rows in flight), its horizontal 3-sum formed with two lane
- * shuffles, and rolling three-row windows give the smoothed row, the thresholded map and the
- * gradient of output row y as rows y + 2 arrive.  Only the interior's neighbourhood is read (the
- * tiled kernel read every row and column), and no LDS or barrier: 290 -> 190 us per configs[1]
- * step (61 k tiled workgroups before), registration 3.20 -> 3.10 ms (profiles/r05x_*).  Same
- * integer sums, so the same result bit for bit. */
+ * 10 % margins, gradient energy over mapped pixels; exact integer sums.  Streamed down a band:
+ * one wave per (60-column band, SG_QGS_ROWS output rows, frame) of the margins' interior, lane l
+ * at column x0 - 2 + l.  Each input row is loaded and stretched once (:139-148: v * (60000 / max),
+ * truncated, clamped at 65535; SG_QGS_PF rows in flight), its horizontal 3-sum formed with two
+ * lane shuffles, and rolling three-row windows give the smoothed row, the thresholded map and the
+ * gradient of output row y as rows y + 2 arrive.  Only the interior's neighbourhood is read, and
+ * no LDS or barrier: 190 us per configs[1] step against 290 for the tiled kernel it replaced
+ * (64 x 16 output tiles through LDS, 61 k workgroups; removed, commit 9b01e1f last contained it),
+ * registration 3.20 -> 3.10 ms (profiles/r05x_*). */
 #define SG_QGS_ROWS 64
 #define SG_QGS_PF 8
 __global__ void __launch_bounds__(64)
@@ -1690,20 +1553,11 @@ static int reg_quality_buffers(sg_ctx *ctx, SgDevice &dv, int nq, int xs, int ys
 /* gradient sums of the subsampled frames on the aux stream (after the work queued on it), read
  * back into the pinned block; aux_ev[0] marks them */
 static int reg_quality_grad(sg_ctx *ctx, SgDevice &dv, int nq, int xs, int ys, const SgQBufs &qb) {
-	/* 2 waves per 64x16 tile: 214 us per 129 frames against 238 (4 waves) and 333 (1 wave),
-	 * scripts/gpu_qgrad.sh */
-	const int gthr = ctx->knobs.qgrad_threads;	/* A/B knob SG_QGRAD_THREADS */
-	if (ctx->knobs.qgrad_stream) {	/* A/B knob SG_QGRAD_STREAM: 0 = the tiled kernel */
-		const int xb = (int)((double)xs * 0.1) + 1, yb = (int)((double)ys * 0.1) + 1;
-		const int wi = xs - 2 * xb, hi = ys - 2 * yb;
-		if (wi > 0 && hi > 0) {
-			hipLaunchKernelGGL(k_quality_grad_s, dim3((wi + 59) / 60, (hi + SG_QGS_ROWS - 1) / SG_QGS_ROWS, nq), dim3(64),
-					0, dv.aux, qb.qbuf, xs, ys, qb.qmax, qb.acc);
-			HIPCHK(hipGetLastError());
-		}
-	} else {
-		hipLaunchKernelGGL(k_quality_grad, dim3((xs + 63) / 64, (ys + SG_QGT - 1) / SG_QGT, nq), dim3(gthr), 0, dv.aux, qb.qbuf,
-				xs, ys, qb.qmax, qb.acc);
+	const int xb = (int)((double)xs * 0.1) + 1, yb = (int)((double)ys * 0.1) + 1;
+	const int wi = xs - 2 * xb, hi = ys - 2 * yb;
+	if (wi > 0 && hi > 0) {
+		hipLaunchKernelGGL(k_quality_grad_s, dim3((wi + 59) / 60, (hi + SG_QGS_ROWS - 1) / SG_QGS_ROWS, nq), dim3(64), 0,
+				dv.aux, qb.qbuf, xs, ys, qb.qmax, qb.acc);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipMemcpyAsync(dv.qacc_h, qb.acc, sizeof(unsigned long long) * 3 * nq, hipMemcpyDeviceToHost, dv.aux));
@@ -1806,10 +1660,8 @@ static const void *const SG_REG_LDS_KERNELS[SG_RK_COUNT] = {
 	(const void *)k_reg_rows_inv_half_argmax<float2, false>, (const void *)k_reg_cols<float2, 8>,
 	(const void *)k_reg_cols<float2, 16>,
 	/* SG_RK_XPOWER32 + SgRegCols32 */
-	(const void *)k_reg_cols_xpower<float2, 8>, (const void *)k_reg_cols_xpower<float2, 8, 8>,
-	(const void *)k_reg_cols_xpower<float2, 16>, (const void *)k_reg_cols_xpower_w<true, 4>,
-	(const void *)k_reg_cols_xpower_w<true, 8>, (const void *)k_reg_cols_xpower_w<false, 4>,
-	(const void *)k_reg_cols_fwd_perm_w, (const void *)k_reg_rows_fwd_half_w<false>,
+	(const void *)k_reg_cols_xpower<float2, 8, 8>, (const void *)k_reg_cols_xpower<float2, 16>,
+	(const void *)k_reg_cols_xpower_w, (const void *)k_reg_cols_fwd_perm_w, (const void *)k_reg_rows_fwd_half_w<false>,
 	(const void *)k_reg_rows_fwd_half_w<true>, (const void *)k_reg_rows_inv_half_w};
 
 /* kernel instances with one argument list, indexed by the plan's decisions */
@@ -1820,12 +1672,9 @@ static constexpr SgInv64Fn SG_INV64_KERNELS[2] = {	/* [candidates] */
 	k_reg_rows_inv_half_argmax<sg_c64, false>, k_reg_rows_inv_half_argmax<sg_c64, true>};
 typedef decltype(&k_reg_cols<float2, 8>) SgCols32Fn;
 static constexpr SgCols32Fn SG_COLS32_KERNELS[2] = {k_reg_cols<float2, 8>, k_reg_cols<float2, 16>};	/* [ept32 == 16] */
-typedef decltype(&k_reg_cols_xpower<float2, 8>) SgXpower32Fn;
-static constexpr SgXpower32Fn SG_XPOWER32_KERNELS[3] = {	/* [SgRegCols32]: the block-level forms */
-	k_reg_cols_xpower<float2, 8>, k_reg_cols_xpower<float2, 8, 8>, k_reg_cols_xpower<float2, 16>};
-typedef decltype(&k_reg_cols_xpower_w<true, 4>) SgXpowerWFn;
-static constexpr SgXpowerWFn SG_XPOWER_WP_KERNELS[2] = {	/* [SgRegCols32 - SG_COLS32_WAVE4_PERM]: the permuted-spectrum forms */
-	k_reg_cols_xpower_w<true, 4>, k_reg_cols_xpower_w<true, 8>};
+typedef decltype(&k_reg_cols_xpower<float2, 8, 8>) SgXpower32Fn;
+static constexpr SgXpower32Fn SG_XPOWER32_KERNELS[2] = {	/* [SgRegCols32]: the block-level forms */
+	k_reg_cols_xpower<float2, 8, 8>, k_reg_cols_xpower<float2, 16>};
 
 /* one registration call on its way through the launch steps */
 struct SgRegRun {
@@ -1856,7 +1705,6 @@ struct SgRegRun {
 	std::vector<SgRegOut> hout;	/* the pairs' results on the host */
 	SgQBufs qfb;			/* the folded quality estimate's buffers */
 	bool ref_pending;	/* set by reg_ref_spectrum32 (the spectrum is on its own stream); cleared by the first reg_half32, which waits for it, or behind the batch loop */
-	bool q_deferred;	/* set by reg_quality_start (SG_REG_Q_DEFERRED); cleared by the first reg_half32, which launches the estimate */
 	bool q_fold_last;	/* set by reg_main_batches for every batch (true on the last); read by reg_half32: the gradient follows */
 	int q_qbase;		/* set by reg_main_batches for every batch (its first frame's entry of qframes); read by reg_half32 */
 	bool q_launched;	/* set by reg_quality_launch or reg_half32's gradient, never cleared; read by reg_quality_readback */
@@ -1958,11 +1806,11 @@ static int reg_carve_workspace(SgRegRun &r) {
 	return SG_OK;
 }
 
-/* aux2: the stream of a concurrent reference spectrum */
+/* aux2: the stream of an fp32 call's reference spectrum */
 static int reg_ref_stream(SgRegRun &r) {
 	sg_ctx *ctx = r.ctx;
 	SgDevice &dv = r.dv;
-	if (r.pl.ref_conc && !dv.aux2) {
+	if (r.pl.fp32 && !dv.aux2) {
 		HIPCHK(hipStreamCreateWithFlags(&dv.aux2, hipStreamNonBlocking));
 		for (int k = 0; k < 2; k++)
 			HIPCHK(hipEventCreateWithFlags(&dv.aux2_ev[k], hipEventDisableTiming));
@@ -2005,12 +1853,9 @@ static int reg_quality_start(SgRegRun &r) {
 		if (int rc = reg_quality_buffers(ctx, r.dv, nq, xs, xs, r.qfb))
 			return rc;
 		HIPCHK(hipMemsetAsync(r.qfb.acc, 0, (size_t)nq * (3 * sizeof(unsigned long long) + sizeof(unsigned int)), r.s));
-	} else if (pl.qroute == SG_REG_Q_DEFERRED) {
-		r.q_deferred = true;
-	} else {
-		return reg_quality_launch(ctx, r.dv, r.s, r.d_sel, pl.S, pl.qframes, &r.q_launched);
+		return SG_OK;
 	}
-	return SG_OK;
+	return reg_quality_launch(ctx, r.dv, r.s, r.d_sel, pl.S, pl.qframes, &r.q_launched);
 }
 
 /* the generic row kernel over np pairs' rows of `data` */
@@ -2045,7 +1890,7 @@ static int reg_ref_spectrum64(SgRegRun &r, unsigned long long *en) {
 			r.d_fa + NP, r.d_fb + NP, S, r.tw, r.spec, en, pl.rpb);
 	HIPCHK(hipGetLastError());
 	hipLaunchKernelGGL((k_reg_cols<sg_c64, 8>), dim3(S / 2 / pl.CWh, 1), dim3(pl.colh_thr), pl.colh_lds, r.s, r.spec, S,
-			pl.logS, pl.CWh, r.tw, 0, pl.xcdmap);
+			pl.logS, pl.CWh, r.tw, 0);
 	HIPCHK(hipGetLastError());
 	return SG_OK;
 }
@@ -2058,12 +1903,9 @@ static int reg_ref_spectrum32(SgRegRun &r) {
 	SgDevice &dv = r.dv;
 	const SgRegPlan &pl = r.pl;
 	const int S = pl.S, NP = pl.NP;
-	hipStream_t rs = r.s;
-	if (pl.ref_conc) {
-		HIPCHK(hipEventRecord(dv.aux2_ev[0], r.s));
-		HIPCHK(hipStreamWaitEvent(dv.aux2, dv.aux2_ev[0], 0));
-		rs = dv.aux2;
-	}
+	const hipStream_t rs = dv.aux2;
+	HIPCHK(hipEventRecord(dv.aux2_ev[0], r.s));
+	HIPCHK(hipStreamWaitEvent(rs, dv.aux2_ev[0], 0));
 	if (r.specp32) {	/* wave-level passes: one row per wave, the columns straight into lane order */
 		reg_fwd_w_launch(r, rs, r.d_fa + NP, r.d_fb + NP, 1, r.spec32, r.energy, 1, 0);
 		HIPCHK(hipGetLastError());
@@ -2073,14 +1915,11 @@ static int reg_ref_spectrum32(SgRegRun &r) {
 				r.d_fa + NP, r.d_fb + NP, S, r.tw32, r.spec32, r.energy, pl.rpb);
 		HIPCHK(hipGetLastError());
 		hipLaunchKernelGGL(SG_COLS32_KERNELS[pl.ept32 == 16], dim3(S / 2 / pl.CW32, 1), dim3(pl.colh_thr32), pl.colh_lds32,
-				rs, r.spec32, S, pl.logS, pl.CW32, r.tw32, 0, pl.xcdmap);
-	}
-	if (pl.ref_conc) {
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(dv.aux2_ev[1], dv.aux2));
-		r.ref_pending = true;
+				rs, r.spec32, S, pl.logS, pl.CW32, r.tw32, 0);
 	}
 	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(dv.aux2_ev[1], rs));
+	r.ref_pending = true;
 	return SG_OK;
 }
 
@@ -2138,7 +1977,7 @@ static int reg_half64(SgRegRun &r, const int *fa, const int *fb, int np, unsigne
 			S, r.tw, r.work, en, pl.rpb);
 	HIPCHK(hipGetLastError());
 	hipLaunchKernelGGL((k_reg_cols_xpower<sg_c64, 8>), dim3(S / pl.CWh, np), dim3(pl.colh_thr), pl.colh_lds, r.s, r.work,
-			(const sg_c64 *)r.spec, S, pl.CWh, r.tw, pl.xcdmap, pl.pb);
+			(const sg_c64 *)r.spec, S, pl.CWh, r.tw);
 	HIPCHK(hipGetLastError());
 	hipLaunchKernelGGL(SG_INV64_KERNELS[cand], dim3(S, np), dim3(pl.row_thr), pl.row_lds, r.s, (const sg_c64 *)r.work, S,
 			r.tw, r.best, cand ? res : (const SgRegOut *)nullptr, cand ? r.cand : (SgCand *)nullptr);
@@ -2146,17 +1985,12 @@ static int reg_half64(SgRegRun &r, const int *fa, const int *fb, int np, unsigne
 	return SG_OK;
 }
 
-/* what the first / last batch's fp32 forward rows are followed by: the deferred quality estimate,
- * the wait for the reference spectrum's stream, the folded estimate's gradient */
+/* what the first / last batch's fp32 forward rows are followed by: the wait for the reference
+ * spectrum's stream, the folded estimate's gradient */
 static int reg_half32_after_rows(SgRegRun &r) {
 	sg_ctx *ctx = r.ctx;
 	SgDevice &dv = r.dv;
 	const SgRegPlan &pl = r.pl;
-	if (r.q_deferred) {	/* SG_REG_QAFTER: the quality estimate beside the column pass instead */
-		r.q_deferred = false;
-		if (int rc = reg_quality_launch(ctx, dv, r.s, r.d_sel, pl.S, pl.qframes, &r.q_launched))
-			return rc;
-	}
 	if (r.ref_pending) {	/* the reference spectrum, from its stream */
 		HIPCHK(hipStreamWaitEvent(r.s, dv.aux2_ev[1], 0));
 		r.ref_pending = false;
@@ -2185,16 +2019,12 @@ static int reg_half32(SgRegRun &r, const int *fa, const int *fb, int np, unsigne
 	HIPCHK(hipGetLastError());
 	if (int rc = reg_half32_after_rows(r))
 		return rc;
-	if (pl.cols32 == SG_COLS32_WAVE4_PERM || pl.cols32 == SG_COLS32_WAVE8_PERM) {	/* S = 2048: the wave-level column pass (SG_REG_WCOL=0: the block-level one, A/B) */
-		const int cw = pl.cols32 == SG_COLS32_WAVE8_PERM ? 8 : 4;	/* 8-column strips: 64-B row segments, one workgroup per CU */
-		hipLaunchKernelGGL(SG_XPOWER_WP_KERNELS[pl.cols32 - SG_COLS32_WAVE4_PERM], dim3(S / cw, np), dim3(64 * cw),
-				cw / 4 * pl.wcol_lds, r.s, r.work32, (const float2 *)r.spec32, (const float2 *)r.specp32, r.tw32, pl.xcdmap);
-	} else if (pl.cols32 == SG_COLS32_WAVE4_LDS) {
-		hipLaunchKernelGGL((k_reg_cols_xpower_w<false, 4>), dim3(S / 4, np), dim3(256), pl.wcol_lds, r.s, r.work32,
-				(const float2 *)r.spec32, (const float2 *)nullptr, r.tw32, pl.xcdmap);
-	} else {	/* 8 elements per thread, 8 at 64 VGPRs (default, SG_REG_COLOCC=1), or 16 */
+	if (pl.cols32 == SG_COLS32_WAVE8_PERM) {	/* S = 2048: the wave-level column pass (SG_REG_WCOL=0: the block-level one, A/B), 8-column strips: 64-B row segments, one workgroup per CU */
+		hipLaunchKernelGGL(k_reg_cols_xpower_w, dim3(S / 8, np), dim3(64 * 8), 2 * pl.wcol_lds, r.s, r.work32,
+				(const float2 *)r.spec32, (const float2 *)r.specp32, r.tw32);
+	} else {	/* 8 elements per thread at 64 VGPRs, or 16 */
 		hipLaunchKernelGGL(SG_XPOWER32_KERNELS[pl.cols32], dim3(S / pl.CW32, np), dim3(pl.colh_thr32), pl.colh_lds32, r.s,
-				r.work32, (const float2 *)r.spec32, S, pl.CW32, r.tw32, pl.xcdmap, 1);
+				r.work32, (const float2 *)r.spec32, S, pl.CW32, r.tw32);
 	}
 	HIPCHK(hipGetLastError());
 	if (pl.wcol)
@@ -2417,7 +2247,7 @@ static int reg_quality_readback(SgRegRun &r, const int *included, double *qualit
 }
 
 /* tables, LDS limits, workspace and pair table of a planned call, then the quality estimate (or
- * its deferral) and the reference spectrum */
+ * the folded one's zeroed sums) and the reference spectrum */
 static int reg_setup(SgRegRun &r) {
 	sg_ctx *ctx = r.ctx;
 	if (int rc = reg_upload_tables64(r))

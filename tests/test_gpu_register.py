@@ -434,10 +434,7 @@ def order_2048(gpu_ctx):
 @pytest.mark.parametrize("env", [
     {"SG_REG_BATCH": "1"},
     {"SG_REG_BATCH": "2"},      # two batches: the folded subsample's base advances, the gradient follows the last
-    {"SG_REG_QFOLD": "0", "SG_REG_QAFTER": "1"},
-    {"SG_REG_REFCONC": "0"},
-    {"SG_REG_SPECP": "0"},
-    {"SG_REG_WCOLW": "4"},
+    {"SG_REG_QFOLD": "0"},      # k_quality_sub and the streamed gradient, queued up front
     {"SG_REG_WCOL": "0", "SG_REG_CW32": "8"},   # the block-level column pass with 16 elements per thread
 ], ids=lambda e: ",".join("%s=%s" % (k[7:], v) for k, v in e.items()))
 def test_register_launch_order_knobs_2048(order_2048, env):
@@ -448,12 +445,11 @@ def test_register_launch_order_knobs_2048(order_2048, env):
 
 
 def test_register_launch_order_knobs_256(gpu_ctx):
-    """S = 256 (the smallest side at which a block-level strip is 4 columns of whole waves): the
-    column pass without the 64-VGPR bound, and one pair per batch over five frames to register"""
+    """S = 256 (the smallest side at which a block-level strip is 4 columns of whole waves): one
+    pair per batch over five frames to register"""
     sel, inc = _order_case(256, 172)
     want = gpu_ctx.register_dft(sel, ref_image=2, included=inc)
-    for env in ({"SG_REG_COLOCC": "0"}, {"SG_REG_BATCH": "1"}):
-        _assert_same_registration(_register_under(env, sel, inc), want)
+    _assert_same_registration(_register_under({"SG_REG_BATCH": "1"}, sel, inc), want)
 
 
 def test_register_launch_order_generic_batches(gpu_ctx):

@@ -84,3 +84,11 @@ def test_retired_names_are_gone():
             assert "dv.host_frames" not in text, name            # the loop stages, not the entry
     ctx = dict(_sources())["sg_ctx.hpp"]
     assert len(re.findall(r"SgBuf host_frames;", ctx)) == 1
+
+
+def test_retired_registration_variants_are_gone():
+    """the registration variants that lost their A/B measurements went with the variables that selected them"""
+    for name, text in _sources():
+        for old in ("SG_REG_SPECP", "SG_REG_WCOLW", "SG_REG_XCD", "SG_REG_PB", "SG_REG_QAFTER", "SG_QGRAD_STREAM",
+                    "SG_QGRAD_THREADS", "SG_REG_REFCONC", "SG_REG_COLOCC", "k_quality_grad("):
+            assert old not in text, (name, old)

@@ -92,7 +92,7 @@ static void test_route_by_side(void) {
 		CHECK(c.pl.gen.npass == 0 && c.pl.tab_total == 4 * (size_t)S && c.pl.logS == (int)lround(log2((double)S)));
 		c.k.reg_fp = 64;
 		CHECK(c.plan() == SG_OK && c.pl.route == SG_REG_HALF64 && !c.pl.fp32 && c.pl.tol_main == -32 && c.pl.esz == 16);
-		CHECK(!c.pl.specp_on && c.pl.qfold == 0 && !c.pl.ref_conc);
+		CHECK(!c.pl.specp_on && c.pl.qfold == 0);
 		c.k.reg_fp = 32;
 		c.k.reg_wcol = 0;
 		CHECK(c.plan() == SG_OK && c.pl.route == SG_REG_HALF32_BLOCK && !c.pl.wcol && !c.pl.specp_on);
@@ -169,7 +169,7 @@ static void test_strips_and_threads(void) {
 		CHECK(c.pl.row_lds == (size_t)(S + S / 8) * 16 && c.pl.row_lds32 == (size_t)(S + S / 8) * 8);
 		CHECK(c.pl.colh_lds == (size_t)c.pl.CWh * (S + S / 8 + 1) * 16);
 		CHECK(c.pl.colh_lds32 == (size_t)c.pl.CW32 * (S + S / 8 + 4) * 8 && (S / 2) % c.pl.CW32 == 0);
-		CHECK(c.pl.wcol_lds == (size_t)4 * 2120 * 8 && c.pl.rpb == 4 && c.pl.xcdmap == 1 && c.pl.pb == 1);
+		CHECK(c.pl.wcol_lds == (size_t)4 * 2120 * 8 && c.pl.rpb == 4);
 	}
 	const int ss[3] = {256, 2048, 4096}, ept[3] = {8, 8, 16}, thr[3] = {128, 1024, 1024};
 	for (int i = 0; i < 3; i++) {
@@ -193,18 +193,11 @@ static void test_strips_and_threads(void) {
 
 static void test_switches(void) {
 	Case a(2048);
-	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_WAVE8_PERM && a.pl.specp_on && a.pl.ref_conc);
-	CHECK(a.pl.qroute == SG_REG_Q_FOLDED && a.pl.qfold == 12);
+	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_WAVE8_PERM && a.pl.specp_on && a.pl.qroute == SG_REG_Q_FOLDED && a.pl.qfold == 12);
 	CHECK(a.pl.spec_bytes == (size_t)2048 * 2048 * (16 + 8 + 4));
-	a.k.reg_wcolw = 4;
-	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_WAVE4_PERM);
-	a.k.reg_specp = 0;
-	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_WAVE4_LDS && !a.pl.specp_on && a.pl.qroute == SG_REG_Q_UPFRONT && a.pl.qfold == 0);
-	CHECK(a.pl.spec_bytes == (size_t)2048 * 2048 * 24);
 	a.k.reg_wcol = 0;
-	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_BLOCK8_OCC);
-	a.k.reg_colocc = 0;
-	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_BLOCK8);
+	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_BLOCK8_OCC && !a.pl.specp_on);
+	CHECK(a.pl.spec_bytes == (size_t)2048 * 2048 * 24 && a.pl.qroute == SG_REG_Q_UPFRONT && a.pl.qfold == 0);
 	a.k.reg_cw32 = 8;
 	CHECK(a.plan() == SG_OK && a.pl.cols32 == SG_COLS32_BLOCK16);
 	Case b(256);
@@ -213,33 +206,44 @@ static void test_switches(void) {
 	CHECK(c.plan() == SG_OK && c.pl.cols32 == SG_COLS32_BLOCK16);
 	/* the quality route */
 	Case f(2048);
-	f.k.reg_qafter = 1;
-	CHECK(f.plan() == SG_OK && f.pl.qroute == SG_REG_Q_FOLDED);	/* folded wins */
-	f.k.reg_qfold = 0;
-	CHECK(f.plan() == SG_OK && f.pl.qroute == SG_REG_Q_DEFERRED && f.pl.qfold == 0);
 	f.k.reg_fp = 64;
+	CHECK(f.plan() == SG_OK && f.pl.qroute == SG_REG_Q_UPFRONT && f.pl.qfold == 0);
+	f.k.reg_qfold = 0;
 	CHECK(f.plan() == SG_OK && f.pl.qroute == SG_REG_Q_UPFRONT);
-	Case g(2048, 1);	/* no pair: nothing to fold into, nothing to defer behind */
-	g.k.reg_qafter = 1;
+	f.k.reg_fp = 32;
+	CHECK(f.plan() == SG_OK && f.pl.qroute == SG_REG_Q_UPFRONT && f.pl.qfold == 0);
+	Case g(2048, 1);	/* no pair: nothing to fold into */
 	CHECK(g.plan() == SG_OK && g.pl.qroute == SG_REG_Q_UPFRONT && g.pl.qfold == 0);
-	Case h(256);
-	h.k.reg_qafter = 1;
-	CHECK(h.plan() == SG_OK && h.pl.qroute == SG_REG_Q_DEFERRED);
 	Case i(60);
-	i.k.reg_qafter = 1;
 	CHECK(i.plan() == SG_OK && i.pl.qroute == SG_REG_Q_UPFRONT);
-	for (const char *off : {"wcol", "specp", "fp"}) {
-		Case q(2048);
-		if (!strcmp(off, "wcol")) q.k.reg_wcol = 0;
-		if (!strcmp(off, "specp")) q.k.reg_specp = 0;
-		if (!strcmp(off, "fp")) q.k.reg_fp = 64;
-		CHECK(q.plan() == SG_OK && q.pl.qroute == SG_REG_Q_UPFRONT && q.pl.qfold == 0);
+}
+
+/* the knobs of the removed A/B variants are no longer read: each set to its old losing value, SgKnobs::read() gives
+ * the default plan.  same_plan lists the decisions by hand: a field added to SgRegPlan belongs here too */
+#define EQ(f) (a.f == b.f)
+static bool same_plan(const SgRegPlan &a, const SgRegPlan &b) {
+	auto attr = [](const SgRegLdsAttr &x, const SgRegLdsAttr &y) { return x.kernel == y.kernel && x.bytes == y.bytes; };
+	return std::equal(a.lds_attrs.begin(), a.lds_attrs.end(), b.lds_attrs.begin(), b.lds_attrs.end(), attr) &&
+		EQ(npairs_total) && EQ(NP) && EQ(route) && EQ(generic) && EQ(fp32) && EQ(wcol) && !memcmp(&a.gen, &b.gen, sizeof a.gen) &&
+		EQ(gen_thr) && EQ(gen_lds) && EQ(gen_fuse) && EQ(plane) && EQ(esz) && EQ(pair_bytes) && EQ(B) && EQ(Bc) && EQ(B64) &&
+		EQ(row_thr) && EQ(row_lds) && EQ(row_lds32) && EQ(CW) && EQ(CWh) && EQ(colh_thr) && EQ(colh_lds) && EQ(CW32) &&
+		EQ(ept32) && EQ(colh_thr32) && EQ(colh_lds32) && EQ(wcol_lds) && EQ(rpw) && EQ(rpb) && EQ(logS) && EQ(tol_main) &&
+		EQ(tgrid) && EQ(cols32) && EQ(qroute) && EQ(qfold) && EQ(specp_on) && EQ(n_tw) && EQ(n_twm) && EQ(n_ch) && EQ(n_bh) &&
+		EQ(tab_total) && EQ(spec_bytes) && EQ(work_bytes) && EQ(o_out) && EQ(o_fab) && EQ(o_en) && EQ(o_cand) && EQ(o_res2) &&
+		EQ(ws) && EQ(pin_res) && EQ(pin_bytes);
+}
+static void test_removed_knobs(void) {
+	const char *knobs[9][2] = {{"SG_REG_SPECP", "0"}, {"SG_REG_WCOLW", "4"}, {"SG_REG_XCD", "0"}, {"SG_REG_PB", "4"},
+		{"SG_REG_QAFTER", "1"}, {"SG_QGRAD_STREAM", "0"}, {"SG_QGRAD_THREADS", "256"}, {"SG_REG_REFCONC", "0"},
+		{"SG_REG_COLOCC", "0"}};
+	for (auto &kv : knobs)
+		setenv(kv[0], kv[1], 1);
+	for (int S : {2048, 1024, 256}) {
+		Case def(S), set(S);	/* def: the knobs as constructed */
+		set.k.read();
+		CHECK(def.plan() == SG_OK && set.plan() == SG_OK && same_plan(def.pl, set.pl) && set.pl.lds_attrs.size() == 16);
+		CHECK(set.pl.cols32 == (S == 2048 ? SG_COLS32_WAVE8_PERM : SG_COLS32_BLOCK8_OCC) && set.pl.qfold == (S == 2048 ? 12 : 0));
 	}
-	Case r(2048);
-	r.k.reg_refconc = 0;
-	r.k.reg_xcd = 0;
-	r.k.reg_pb = 3;
-	CHECK(r.plan() == SG_OK && !r.pl.ref_conc && r.pl.xcdmap == 0 && r.pl.pb == 3);
 }
 
 /* ---- the invariant sweep ---- */
@@ -288,9 +292,7 @@ static void check_invariants(Case &c) {
 	CHECK((pl.qroute == SG_REG_Q_FOLDED) == (pl.qfold != 0));
 }
 
-struct KnobSet {
-	int path, genfuse, wcol, fp, qfold, batch, qafter, refconc, specp, wcolw, cw32, colocc;
-};
+struct KnobSet { int path, genfuse, wcol, fp, qfold, batch, cw32; };
 
 static void test_sweep(void) {
 	std::vector<int> sides;
@@ -301,12 +303,9 @@ static void test_sweep(void) {
 	sides.insert(sides.end(), other, other + 40);
 	/* the defaults, then each knob value a GPU test sets */
 	const KnobSet sets[] = {
-		{2, 1, 1, 32, 12, 0, 0, 1, 1, 8, 4, 1}, {3, 1, 1, 32, 12, 0, 0, 1, 1, 8, 4, 1}, {2, 0, 1, 32, 12, 0, 0, 1, 1, 8, 4, 1},
-		{2, 1, 0, 32, 12, 0, 0, 1, 1, 8, 4, 1}, {2, 1, 1, 64, 12, 0, 0, 1, 1, 8, 4, 1}, {3, 1, 1, 64, 12, 0, 0, 1, 1, 8, 4, 1},
-		{2, 1, 1, 32, 0, 0, 0, 1, 1, 8, 4, 1}, {2, 1, 1, 32, 3, 0, 0, 1, 1, 8, 4, 1}, {2, 1, 1, 32, 6, 0, 0, 1, 1, 8, 4, 1},
-		{2, 1, 1, 32, 12, 1, 0, 1, 1, 8, 4, 1}, {2, 1, 1, 32, 12, 2, 0, 1, 1, 8, 4, 1}, {2, 1, 1, 32, 0, 0, 1, 1, 1, 8, 4, 1},
-		{2, 1, 1, 32, 12, 0, 0, 0, 1, 8, 4, 1}, {2, 1, 1, 32, 12, 0, 0, 1, 0, 8, 4, 1}, {2, 1, 1, 32, 12, 0, 0, 1, 1, 4, 4, 1},
-		{2, 1, 0, 32, 12, 0, 0, 1, 1, 8, 8, 1}, {2, 1, 1, 32, 12, 0, 0, 1, 1, 8, 4, 0}};
+		{2, 1, 1, 32, 12, 0, 4}, {3, 1, 1, 32, 12, 0, 4}, {2, 0, 1, 32, 12, 0, 4}, {2, 1, 0, 32, 12, 0, 4},
+		{2, 1, 1, 64, 12, 0, 4}, {3, 1, 1, 64, 12, 0, 4}, {2, 1, 1, 32, 0, 0, 4}, {2, 1, 1, 32, 3, 0, 4},
+		{2, 1, 1, 32, 6, 0, 4}, {2, 1, 1, 32, 12, 1, 4}, {2, 1, 1, 32, 12, 2, 4}, {2, 1, 0, 32, 12, 0, 8}};
 	int planned = 0;
 	for (int S : sides)
 		for (const KnobSet &ks : sets)
@@ -315,12 +314,11 @@ static void test_sweep(void) {
 				if (shape == 0)
 					c.inc = {1, 1, 1, 1, 0, 1, 1};
 				c.k.reg_path = ks.path, c.k.reg_genfuse = ks.genfuse, c.k.reg_wcol = ks.wcol, c.k.reg_fp = ks.fp;
-				c.k.reg_qfold = ks.qfold, c.k.reg_batch = ks.batch, c.k.reg_qafter = ks.qafter, c.k.reg_refconc = ks.refconc;
-				c.k.reg_specp = ks.specp, c.k.reg_wcolw = ks.wcolw, c.k.reg_cw32 = ks.cw32, c.k.reg_colocc = ks.colocc;
+				c.k.reg_qfold = ks.qfold, c.k.reg_batch = ks.batch, c.k.reg_cw32 = ks.cw32;
 				check_invariants(c);
 				planned++;
 			}
-	CHECK(planned == (11 + 40) * 17 * 3);
+	CHECK(planned == (11 + 40) * 12 * 3);
 }
 
 /* ---- the host tables ---- */
@@ -402,6 +400,7 @@ int main(void) {
 	test_sweep();
 	test_twiddles();
 	test_bluestein();
+	test_removed_knobs();	/* last: it leaves the variables set */
 	printf("checks=%d bad=%d\n", checks, bad);
 	return bad != 0;
 }
