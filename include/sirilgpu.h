@@ -732,6 +732,104 @@ int sg_quality_normalize(int nframes, int ref_image, const double *quality_raw, 
 int sg_quality_select(int nframes, const double *quality, const int *included, double percent, double *threshold,
 		int *selected, int *nselected, char *msg, int msg_len);
 
+/*
+ * One-star registration: seqpsf (src/io/sequence.c:1627-1820) and register_shift_fwhm
+ * (src/registration/registration.c:406-490) on frames resident in HBM: the PSF of one star in a
+ * rectangular selection of every frame, and the shifts that align the star.  Per processed frame
+ * (frames outside `included` get SG_SEQPSF_EXCLUDED and nothing else), with the area (x, y, w, h) in
+ * display (top-down) coordinates and W x H frames bottom-up in memory:
+ *   1. the area: the call's; REGISTERED first applies x -= shiftx[f], y += shifty[f]
+ *      (core/processing.c:85-137); FOLLOW_STAR starts from the carried area of step 6.  Then
+ *      enforce_area_in_image (sequence.c:1123-1130) on a local copy: x < 0 -> 0, y < 0 -> 0,
+ *      x + w > W -> W - w, y + h > H -> H - h.
+ *   2. the box z[i][j] = memory row H - y - h + i, column x + j; i < h rows, j < w columns
+ *      (PSF.c:583-608).  Not transposed, unlike peaker's box.
+ *   3. bg = background() (core/siril.c:1173-1192): the median of statistics(STATS_BASIC,
+ *      STATS_ZERO_NULLCHECK) (statistics.c:47-63, 207-256; histogram.c:129-150): ngood = the non-zero
+ *      pixels, 65536 bins over [0, 65535) (65535 is not binned but counts in ngood), from bin 1 the
+ *      first bin whose running count exceeds ngood * 0.5, else 0; ngood = 0 gives bg = 0.0 and the
+ *      fit goes on.
+ *   4. psf_minimiz_no_angle (PSF.c:46-157, 314-428): psf_init_data on the h x w box (getMedian3x3
+ *      with its zero padding and its 8 - n - 1 offset, the first maximum in row-major order, the
+ *      half-maximum walks bounded by NbRows - 1 / NbCols - 1), x_init = {bg, max, (jj1 + jj2 + 2) / 2,
+ *      (ii1 + ii2 + 2) / 2, (size_t)(SQR(jj1 - jj2) / 4 / ln 2), (size_t)(SQR(ii1 - ii2) / 4 / ln 2)},
+ *      lmsder on psf_Gaussian_f / _df as siril-0.9_amd/csrc/sg_psf.h restates it; n = w h <= 6: no PSF.
+ *   5. psf_minimiz_angle (PSF.c:229-309, 434-559) when |SX - SY| >= 0.01 on the result of 4: lmsder
+ *      with p = 7 on psf_Gaussian_f_an / _df_an literally (columns 2 and 3 keep cos(alpha), column 6
+ *      as written), from {B, A, x0, y0, SX, SY, 0}, at most 10 iterations, test_delta(1e-4, 1e-4);
+ *      angle = -alpha 180 / pi folded by `while (fabs(angle) > 90) angle -+= 90`; mag =
+ *      -2.5 log10(sum(z - B)); fwhm = sqrt(S / 2) 2 sqrt(2 ln 2); rmse at the final x (the departure
+ *      sg_findstar_fit documents).
+ *   6. psf_global_minimisation (PSF.c:620-662): sy > sx swaps sx / sy and fwhmx / fwhmy, and a fitted
+ *      angle != 0 gets -= 90 when positive, else += 90; B, A, rmse divided by norm; no PSF when a FWHM
+ *      is not finite or <= 0; psf_update_units as the two factors; xpos = x0 + area.x, ypos = area.y +
+ *      area.h - y0 with the clamped area of 1.  FOLLOW_STAR: the carried (unclamped) area becomes
+ *      x = round_to_int(xpos) - w / 2, y = round_to_int(ypos) - h / 2 (integer division;
+ *      core/utils.c:60-66).
+ *   7. a frame with no PSF makes the reference abort the sequence and store nothing; here its status
+ *      says so, and in FOLLOW_STAR the frames after it are not run (SG_SEQPSF_NOT_RUN).
+ * Departure: the angle fold is bounded; a fold of more than 8 steps reports SG_FIT_NONFINITE.
+ * ORIGINAL and REGISTERED run one workgroup per frame; FOLLOW_STAR is one launch of one workgroup
+ * that walks the included frames in index order with no host look between them.
+ * Frames are read in place with the pitches of sg_register_ecc_u16_device and never written.
+ * Refused before any device work: SG_ERR_SIZE for w or h < 1 or > SG_SEQPSF_MAX_SIDE, w > W, h > H,
+ * nframes < 1, and the pitch and size conditions sg_register_ecc_u16_device refuses; SG_ERR_GENERIC
+ * for an unknown framing, REGISTERED without shifts, norm != 65535, a scale that is not finite, a
+ * missing pointer.  w h <= 6 is no error: every frame gets SG_FIT_NOT_ENOUGH_PIXELS (and stops a
+ * FOLLOW_STAR chain at its first frame).
+ * Left to the caller: photometry (for_photometry = TRUE), the relative uncertainties, 8-bit
+ * statistics, date_obs and exposure bookkeeping, areas above 128 pixels a side, sharding over devices.
+ */
+enum { SG_SEQPSF_ORIGINAL = 0, SG_SEQPSF_REGISTERED = 1, SG_SEQPSF_FOLLOW_STAR = 2 };
+#define SG_SEQPSF_MAX_SIDE 128     /* w, h <= 128: the box (<= 16384 px, 32 KiB as u16) lives in LDS */
+/* statuses: the SG_FIT_* values 0..3 keep their meaning (0 = a PSF), plus */
+enum { SG_SEQPSF_NOT_RUN = 6,      /* FOLLOW_STAR: a frame after the one that stopped the chain */
+       SG_SEQPSF_EXCLUDED = 7 };
+
+typedef struct {
+	int framing;               /* SG_SEQPSF_* */
+	sg_rect area;              /* display coordinates; need not lie inside the image (step 1) */
+	double norm;               /* 65535 (255 refused: 8-bit statistics are out of scope) */
+	double fwhm_scale_x, fwhm_scale_y;
+	int fit_angle;             /* 1 = seqpsf; 0 stops after step 4 (diagnosis, and the tests' way to pin step 4 alone) */
+} sg_seqpsf_desc;
+
+typedef struct {
+	int32_t status, angle_fitted, iters, iters_angle;
+	int32_t area_x, area_y;    /* the clamped area the box was read from */
+	int64_t ngood;
+	double bg, init[6], noangle[6];   /* start values; x after the 6-parameter fit */
+	double B, A, x0, y0, sx, sy, fwhmx, fwhmy, angle, mag, rmse, xpos, ypos;
+} sg_seqpsf_frame;
+
+/* frame f, row r, column x at d_frames[f * frame_pitch + r * row_pitch + x] (elements; 0 = tight).
+ * included: host [nframes], NULL = all.  reg_shiftx / reg_shifty: host [nframes], required for
+ * REGISTERED only.  per_frame: host [nframes].  area_carry may be NULL; when non-NULL and FOLLOW_STAR
+ * it replaces desc->area's x and y as the chain's starting (unclamped) area on entry, and on return
+ * holds the carried area after the last frame run ({x, y} of desc->area in the other framings).
+ * SG_OK even when frames have no PSF: the statuses say so.  Synchronous; the same bits on every run. */
+int sg_seqpsf_u16_device(sg_ctx *ctx, int dev_index, const sg_seqpsf_desc *desc, const uint16_t *d_frames,
+		int64_t frame_pitch, int64_t row_pitch, int W, int H, int nframes, const int *included, const int *reg_shiftx,
+		const int *reg_shifty, sg_seqpsf_frame *per_frame, sg_rect *area_carry, void *stream);
+/* the same on host frames with the same pitches, uploaded in batches, on device 0 of the context; a
+ * FOLLOW_STAR chain is carried from batch to batch, so every batch size gives the same bits, and the
+ * frames of the batches after a stopped chain are marked without being uploaded */
+int sg_seqpsf_u16(sg_ctx *ctx, const sg_seqpsf_desc *desc, const uint16_t *frames, int64_t frame_pitch, int64_t row_pitch,
+		int W, int H, int nframes, const int *included, const int *reg_shiftx, const int *reg_shifty,
+		sg_seqpsf_frame *per_frame, sg_rect *area_carry);
+/* the last seqpsf call on that device: device time (HIP events) and kernel launches; after the host
+ * entry, the sums over its batches.  Either pointer may be NULL. */
+int sg_seqpsf_last_times(sg_ctx *ctx, int dev_index, double *ms, int *launches);
+/* register_shift_fwhm's second step from the records, host only, no context.  ref_image < 0 means 0.
+ * Returns 1 when a frame that is not excluded has a status other than 0 (seqpsf aborted; outputs
+ * untouched), -1 when the reference frame is excluded (outputs untouched), else 0 with: shifts 0 for
+ * the reference and the excluded frames, else shiftx = round_to_int(ref.xpos - xpos), shifty =
+ * round_to_int(ypos - ref.ypos); fwhm[f] = fwhmx (0 for excluded frames); the best frame by the loop
+ * as written: it starts at the reference's fwhmx and is replaced when fwhm[f] < fwhm_min && fwhm[f] >
+ * 0, scanning in frame order without revisiting the reference.  fwhm, best_index, best_fwhm may be NULL. */
+int sg_seqpsf_shifts(int nframes, int ref_image, const sg_seqpsf_frame *per_frame, int *shiftx, int *shifty, double *fwhm,
+		int *best_index, double *best_fwhm);
+
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]
  * (frame_stride 0 = nb_layers*height*width). */

@@ -134,6 +134,11 @@ struct SgDevice {
 	SgBuf quality_work;
 	double quality_ms = 0.;
 	int quality_route = 0, quality_launches = 0;
+	/* one-star registration (sg_seqpsf.hip): the per-frame table and records; the last call's device
+	 * span and launches */
+	SgBuf seqpsf_work;
+	double seqpsf_ms = 0.;
+	int seqpsf_launches = 0;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };

@@ -153,6 +153,23 @@ class WarpSeqDesc(ctypes.Structure):
 WARP_SKIP, WARP_APPLY, WARP_COPY = 0, 1, 2
 
 
+class SeqpsfDesc(ctypes.Structure):
+    """sg_seqpsf_desc"""
+    _fields_ = [("framing", ctypes.c_int), ("area", Rect), ("norm", ctypes.c_double), ("fwhm_scale_x", ctypes.c_double),
+                ("fwhm_scale_y", ctypes.c_double), ("fit_angle", ctypes.c_int)]
+
+
+SEQPSF_ORIGINAL, SEQPSF_REGISTERED, SEQPSF_FOLLOW_STAR = 0, 1, 2
+SEQPSF_NOT_RUN, SEQPSF_EXCLUDED = 6, 7        # statuses beside SG_FIT_* 0 .. 3
+SEQPSF_MAX_SIDE = 128
+SEQPSF_FIELDS = ("B", "A", "x0", "y0", "sx", "sy", "fwhmx", "fwhmy", "angle", "mag", "rmse", "xpos", "ypos")
+# sg_seqpsf_frame as a numpy structured type
+SEQPSF_DTYPE = np.dtype([("status", "<i4"), ("angle_fitted", "<i4"), ("iters", "<i4"), ("iters_angle", "<i4"),
+                         ("area_x", "<i4"), ("area_y", "<i4"), ("ngood", "<i8"), ("bg", "<f8"), ("init", "<f8", (6,)),
+                         ("noangle", "<f8", (6,))] + [(k, "<f8") for k in SEQPSF_FIELDS])
+assert SEQPSF_DTYPE.itemsize == 240
+
+
 # every symbol include/sirilgpu.h and include/sirilgpu_io.h declare
 EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_u16_device",
            "sg_stack_u16_device_async", "sg_stack_collect", "sg_stack_wait_tail", "sg_device_count",
@@ -168,7 +185,8 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_findstar_fit_device", "sg_findstar_fit", "sg_register_ecc_u16_device", "sg_register_ecc_u16",
            "sg_register_ecc_last_times", "sg_cosme_autodetect_device", "sg_cosme_autodetect", "sg_cosme_last_times",
            "sg_quality_u16_device", "sg_quality_u16", "sg_quality_last_times", "sg_quality_normalize", "sg_quality_select",
-           "sg_warp_frames_u16_device", "sg_warp_frames_u16", "sg_warp_frames_last_times"]
+           "sg_warp_frames_u16_device", "sg_warp_frames_u16", "sg_warp_frames_last_times",
+           "sg_seqpsf_u16_device", "sg_seqpsf_u16", "sg_seqpsf_last_times", "sg_seqpsf_shifts"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -336,6 +354,17 @@ def load():
     lib.sg_quality_select.argtypes = [ctypes.c_int, P, P, ctypes.c_double, ctypes.POINTER(ctypes.c_double), P,
                                       ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, ctypes.c_int]
     lib.sg_quality_select.restype = ctypes.c_int
+    lib.sg_seqpsf_u16_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(SeqpsfDesc), P, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, P, ctypes.POINTER(Rect), P]
+    lib.sg_seqpsf_u16_device.restype = ctypes.c_int
+    lib.sg_seqpsf_u16.argtypes = [P, ctypes.POINTER(SeqpsfDesc), P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, P, P, P, P, ctypes.POINTER(Rect)]
+    lib.sg_seqpsf_u16.restype = ctypes.c_int
+    lib.sg_seqpsf_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+    lib.sg_seqpsf_last_times.restype = ctypes.c_int
+    lib.sg_seqpsf_shifts.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P, ctypes.POINTER(ctypes.c_int),
+                                     ctypes.POINTER(ctypes.c_double)]
+    lib.sg_seqpsf_shifts.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -898,6 +927,54 @@ class Context:
                                           inc.ctypes.data_as(P) if inc is not None else None, ctypes.byref(out))
         return rc, res
 
+    @staticmethod
+    def _seqpsf_args(nframes, area, framing, included, reg_shifts, norm, scales, fit_angle, carry):
+        d = SeqpsfDesc(framing, Rect(*[int(v) for v in area]), norm, scales[0], scales[1], 1 if fit_angle else 0)
+        inc = None if included is None else np.ascontiguousarray(included, dtype=np.int32)
+        rsx = rsy = None
+        if reg_shifts is not None:
+            rsx = np.ascontiguousarray(reg_shifts[0], dtype=np.int32)
+            rsy = np.ascontiguousarray(reg_shifts[1], dtype=np.int32)
+        rec = np.zeros(max(nframes, 1), dtype=SEQPSF_DTYPE)
+        cx, cy = carry if carry is not None else area[:2]      # the chain starts at the area unless told otherwise
+        cr = Rect(int(cx), int(cy), int(area[2]), int(area[3]))
+        P = ctypes.c_void_p
+        ptr = lambda a: a.ctypes.data_as(P) if a is not None else None
+        return d, rec, cr, (ptr(inc), ptr(rsx), ptr(rsy)), (inc, rsx, rsy)
+
+    def seqpsf_device(self, d_frames, nframes, H, W, area, framing=SEQPSF_ORIGINAL, included=None, reg_shifts=None,
+                      norm=65535.0, scales=(1.0, 1.0), fit_angle=True, carry=None, frame_pitch=0, row_pitch=0, stream=None,
+                      dev_index=0):
+        """seqpsf's per-frame work on resident frames read in place (sg_seqpsf_u16_device): the PSF of the star
+        in `area` = (x, y, w, h), display coordinates, of every included frame.  reg_shifts = (shiftx, shifty) for
+        SEQPSF_REGISTERED; carry = (x, y) starts a SEQPSF_FOLLOW_STAR chain there instead of at the area.
+        Returns (rc, records as a SEQPSF_DTYPE array, the carried area (x, y))."""
+        d, rec, cr, ptrs, keep = self._seqpsf_args(nframes, area, framing, included, reg_shifts, norm, scales, fit_angle, carry)
+        P = ctypes.c_void_p
+        rc = self.lib.sg_seqpsf_u16_device(self.ctx, dev_index, ctypes.byref(d), P(d_frames), frame_pitch, row_pitch, W, H,
+                                           nframes, ptrs[0], ptrs[1], ptrs[2], rec.ctypes.data_as(P),
+                                           ctypes.byref(cr), P(stream) if stream else None)
+        return rc, rec[:max(nframes, 0)], (cr.x, cr.y)
+
+    def seqpsf(self, frames, area, framing=SEQPSF_ORIGINAL, included=None, reg_shifts=None, norm=65535.0,
+               scales=(1.0, 1.0), fit_angle=True, carry=None, layer=0):
+        """the same on host frames [N][H][W] or [N][C][H][W] u16, layer `layer` (sg_seqpsf_u16)"""
+        frames = np.ascontiguousarray(frames, dtype=np.uint16)
+        if frames.ndim == 3:
+            frames = frames[:, None]
+        N, C, H, W = frames.shape
+        d, rec, cr, ptrs, keep = self._seqpsf_args(N, area, framing, included, reg_shifts, norm, scales, fit_angle, carry)
+        P = ctypes.c_void_p
+        rc = self.lib.sg_seqpsf_u16(self.ctx, ctypes.byref(d), P(frames.ctypes.data + layer * H * W * 2), C * H * W, W, W, H, N,
+                                    ptrs[0], ptrs[1], ptrs[2], rec.ctypes.data_as(P), ctypes.byref(cr))
+        return rc, rec[:N], (cr.x, cr.y)
+
+    def seqpsf_last_times(self, dev_index=0):
+        """(device ms, kernel launches) of the last seqpsf call on that device; after seqpsf(), summed over its batches"""
+        a, n = ctypes.c_double(), ctypes.c_int()
+        self.check(self.lib.sg_seqpsf_last_times(self.ctx, dev_index, ctypes.byref(a), ctypes.byref(n)), "sg_seqpsf_last_times")
+        return a.value, n.value
+
     def cosme_autodetect_device(self, d_frames, nframes, C, H, W, sig=(3.0, 3.0), amount=1.0, is_cfa=False,
                                 frame_stride=0, stream=None, dev_index=0):
         """seqfind_cosme's per-frame work (autoDetect on every layer) on resident frames, in place
@@ -1106,6 +1183,22 @@ class Prepro:
 
     def __exit__(self, *a):
         self.close()
+
+
+def seqpsf_shifts(records, ref_image=0):
+    """register_shift_fwhm's second step from seqpsf's records (sg_seqpsf_shifts, host only).  Returns (rc, shiftx,
+    shifty, fwhm, best index, best fwhm); rc = 1: a frame has no PSF (the reference aborts), -1: the reference frame
+    is excluded; the arrays are then None"""
+    rec = np.ascontiguousarray(records, dtype=SEQPSF_DTYPE)
+    n = len(rec)
+    sx, sy, fw = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64)
+    bi, bf = ctypes.c_int(-1), ctypes.c_double(0.0)
+    P = ctypes.c_void_p
+    rc = load().sg_seqpsf_shifts(n, ref_image, rec.ctypes.data_as(P), sx.ctypes.data_as(P), sy.ctypes.data_as(P),
+                                 fw.ctypes.data_as(P), ctypes.byref(bi), ctypes.byref(bf))
+    if rc != 0:
+        return rc, None, None, None, None, None
+    return rc, sx, sy, fw, bi.value, bf.value
 
 
 def compute_normalization(mode, location, scale, ref_image=0):

@@ -1,0 +1,754 @@
+"""numpy fp64 restatement of Siril 0.9's seqpsf and of register_shift_fwhm's second step
+(src/io/sequence.c:1627-1820, 1123-1130; src/core/processing.c:85-137; src/algos/PSF.c:46-157, 229-309,
+434-559, 583-662; src/core/siril.c:1173-1192; src/algos/statistics.c:47-63, 207-256;
+src/gui/histogram.c:129-150; src/registration/registration.c:406-490; src/core/utils.c:60-66), the
+oracle of sg_seqpsf_u16* / sg_seqpsf_shifts (include/sirilgpu.h) and of siril-0.9_amd/csrc/sg_seqpsf.h.
+
+  piece                                here
+  enforce_area_in_image, the framings  enforce_area, seqpsf
+  psf_get_minimisation's matrix        box_of
+  background / statistics              background (the 65536-bin histogram, as written)
+  psf_init_data                        psf_ref.init_literal (it already takes an h x w matrix)
+  psf_Gaussian_f / _df                 psf_ref.model
+  psf_Gaussian_f_an / _df_an           model_angle (the reference's formulas, as written)
+  lmsder, p = 6 and p = 7              lm (psf_ref.lm with the parameter count left open)
+  psf_minimiz_angle's and psf_global_minimisation's finish, the hook     fit_box
+  register_shift_fwhm :424-489         shifts
+
+Frames are [H][W] uint16 in memory order (row 0 is the display's bottom row); areas are (x, y, w, h)
+in display coordinates.
+
+Tolerance, by the method of psf_ref: VARIANTS change one thing each in the arithmetic the device does
+differently (the sums' order as the device's: partials strided over THREADS threads, a butterfly per
+wave, the waves in order; QR instead of Cholesky; exp moved by one ulp; fused sums).
+  - A frame is branch-stable when all variants agree on status, both iteration counts, both accept /
+    reject traces, angle_fitted, the swap and the area, and none of the |SX - SY| >= 0.01 test, the
+    swap, the angle fold, the FWHM test and the round_to_int of step 6 (and of step 8, see
+    shift_margins) lies within 100 * TOL of flipping.
+  - SPREAD_MEASURED is the largest relative spread (denominator max(|v|, 1)) of any fp field across
+    the variants over the stable frames of every case of CASES; TOL = 16 x it.
+    tests/test_seqpsf_cpu.py recomputes it and holds it within TOL / 16.
+"""
+import math
+
+import numpy as np
+
+import psf_ref as pr
+
+F64 = np.float64
+MAX_ITER, MAX_INNER, MAX_LMPAR = 10, 10, 10
+DBL_MIN = 2.2250738585072014e-308
+EPSILON = 0.01
+MAX_FOLD = 8
+THREADS = 256                       # SGQ_THREADS of sg_seqpsf_plan.hpp
+
+ORIGINAL, REGISTERED, FOLLOW_STAR = 0, 1, 2
+FIT_STAR, FIT_NOT_ENOUGH_PIXELS, FIT_NONFINITE, FIT_BAD_FWHM = 0, 1, 2, 3
+NOT_RUN, EXCLUDED = 6, 7
+
+# measured by tests/test_seqpsf_cpu.py::test_spread_within_tol over CASES (see the docstring)
+SPREAD_MEASURED = 1.23e-12      # measured 1.2251e-12 (drift_original, frame 5: the star has left the area), rounded up
+TOL = 16 * SPREAD_MEASURED
+# restatement against scipy.optimize.least_squares run to 1e-12 from the same start, p = 7, on boxes
+# where the delta test was met before the cap (tests/test_seqpsf_cpu.py::test_angle_fit_is_a_working_lm)
+LSQ_DIFF_MEASURED = 2.09e-5     # measured 2.0882e-05 over 30 converged boxes, rounded up
+LSQ_BOUND = 4 * LSQ_DIFF_MEASURED
+
+FIELDS = ("B", "A", "x0", "y0", "sx", "sy", "fwhmx", "fwhmy", "angle", "mag", "rmse", "xpos", "ypos")
+INT_FIELDS = ("status", "angle_fitted", "iters", "iters_angle", "area_x", "area_y", "ngood")
+
+BASE = dict(sums="seq", linalg="chol", exp="libm", fma="off")
+VARIANTS = {
+    "base": BASE,
+    "device": dict(BASE, sums="device"),
+    "qr": dict(BASE, linalg="qr"),
+    "exp_ulp": dict(BASE, exp="ulp"),
+    "fused": dict(BASE, fma="fused"),
+}
+ALL_VARIANTS = tuple(VARIANTS)
+ULP_SEED = 20262
+
+
+# ---------------------------------------------------------------------------- areas and the box
+
+def round_to_int(x):
+    """utils.c:60-66"""
+    return int(x + 0.5) if x >= 0.0 else int(x - 0.5)
+
+
+def enforce_area(W, H, area):
+    """enforce_area_in_image (sequence.c:1123-1130) on a copy"""
+    x, y, w, h = area
+    if x < 0:
+        x = 0
+    if y < 0:
+        y = 0
+    if x + w > W:
+        x = W - w
+    if y + h > H:
+        y = H - h
+    return (x, y, w, h)
+
+
+def box_of(frame, area):
+    """psf_get_minimisation :591-602: z[i][j] = memory row H - y - h + i, column x + j"""
+    H = frame.shape[0]
+    x, y, w, h = area
+    return np.ascontiguousarray(frame[H - y - h:H - y, x:x + w])
+
+
+def background(box):
+    """background() of the box: (ngood, bg).  statistics(STATS_BASIC, STATS_ZERO_NULLCHECK): ngood = the
+    non-zero pixels; the histogram has 65536 bins over [0, 65535), so 65535 is outside it; from bin 1,
+    the first bin whose running count exceeds ngood * 0.5, else 0; no statistics (ngood = 0): 0.0"""
+    v = np.asarray(box).reshape(-1).astype(np.int64)
+    ngood = int((v != 0).sum())
+    if ngood == 0:
+        return 0, 0.0
+    hist = np.bincount(v[v < 65535], minlength=65536).astype(F64)
+    total, median = 0.0, 0.0
+    for i in range(1, 65536):
+        total += hist[i]
+        if total > ngood * 0.5:
+            median = float(i)
+            break
+    return ngood, median
+
+
+# ---------------------------------------------------------------------------- the angle model
+
+def model_angle(x, z, rng=None):
+    """psf_Gaussian_f_an / psf_Gaussian_df_an (sigma = 1) over the box as written: (f [n], J [n][7])"""
+    h, w = z.shape
+    jj = np.arange(1, w + 1, dtype=F64)[None, :] + 0 * np.arange(h, dtype=F64)[:, None]
+    ii = np.arange(1, h + 1, dtype=F64)[:, None] + 0 * np.arange(w, dtype=F64)[None, :]
+    B, A, x0, y0, SX, SY, alpha = [F64(v) for v in x]
+    with np.errstate(all="ignore"):
+        ca, sa = np.cos(alpha), np.sin(alpha)
+        tmpx = ca * (jj - x0) - sa * (ii - y0) + x0
+        tmpy = sa * (jj - x0) + ca * (ii - y0) + y0
+        dx, dy = tmpx - x0, tmpy - y0
+        c = np.exp(-(dx * dx / SX + dy * dy / SY))
+        if rng is not None:
+            c = np.nextafter(c, np.where(rng.integers(0, 2, size=c.shape) == 1, np.inf, -np.inf))
+        f = B + A * c - z
+        derx = -sa * (jj - x0) - ca * (ii - y0)
+        dery = ca * (jj - x0) - sa * (ii - y0)
+        J = np.stack([np.ones_like(c), c, A * c * 2 * dx / SX * ca, A * c * 2 * dy / SY * ca,
+                      A * c * (dx * dx) / (SX * SX), A * c * (dy * dy) / (SY * SY),
+                      -A * c * (2 * dx / SX * derx + 2 * dy / SY * dery)], axis=-1)
+    return f.reshape(-1), J.reshape(-1, 7)
+
+
+def model(x, z, rng=None):
+    return pr.model(x, z, rng) if len(x) == 6 else model_angle(x, z, rng)
+
+
+# ---------------------------------------------------------------------------- sums
+
+def _total(cols, v):
+    """the sum over pixels of each column of cols [n][k] as the variant sums it"""
+    with np.errstate(all="ignore"):
+        if v["sums"] != "device" or v["fma"] == "fused":
+            return pr._total(cols, dict(v, sums="seq"))
+        n, k = cols.shape
+        pad = (-n) % THREADS
+        th = np.concatenate([cols, np.zeros((pad, k), dtype=cols.dtype)]).reshape(-1, THREADS, k)
+        part = np.cumsum(th, axis=0)[-1].reshape(THREADS // 64, 64, k)   # thread t holds pixels t, t + THREADS, ..
+        idx = np.arange(64)
+        for o in (32, 16, 8, 4, 2, 1):
+            part = part + part[:, idx ^ o]
+        return np.cumsum(part[:, 0], axis=0)[-1]                          # the waves in order
+
+
+def sums(x, z, v, rng=None):
+    """(a [p][p] = J^T J, g [p] = J^T f, ff = |f|^2, J)"""
+    p = len(x)
+    f, J = model(x, z, rng)
+    with np.errstate(all="ignore"):
+        cols = [pr._products(J[:, i], J[:, j], v) for i in range(p) for j in range(i, p)]
+        cols += [pr._products(J[:, i], f, v) for i in range(p)]
+        cols.append(pr._products(f, f, v))
+        t = _total(np.stack(cols, axis=1), v)
+    a = np.zeros((p, p), dtype=F64)
+    k = 0
+    for i in range(p):
+        for j in range(i, p):
+            a[i, j] = a[j, i] = t[k]
+            k += 1
+    return a, t[k:k + p].copy(), F64(t[k + p]), J
+
+
+def resid(x, z, v, rng=None):
+    f, _ = model(x, z, rng)
+    with np.errstate(all="ignore"):
+        return F64(_total(pr._products(f, f, v)[:, None], v)[0])
+
+
+def flux(z, B, v):
+    with np.errstate(all="ignore"):
+        return F64(_total((z.reshape(-1) - F64(B))[:, None], dict(v, fma="off"))[0])
+
+
+# ---------------------------------------------------------------------------- p x p linear algebra (psf_ref's)
+
+def _chol(At, par):
+    p = At.shape[0]
+    L = np.zeros((p, p), dtype=F64)
+    ri = np.zeros(p, dtype=F64)
+    ok = True
+    with np.errstate(all="ignore"):
+        for j in range(p):
+            d = At[j, j] + par
+            for k in range(j):
+                d = d - L[j, k] * L[j, k]
+            if not d > 0.0:
+                ok = False
+            l = np.sqrt(d)
+            rl = 1.0 / l
+            L[j, j] = l
+            ri[j] = rl
+            for i in range(j + 1, p):
+                val = At[i, j]
+                for k in range(j):
+                    val = val - L[i, k] * L[j, k]
+                L[i, j] = val * rl
+    return L, ri, ok
+
+
+def _fwd(L, ri, w):
+    w = w.copy()
+    with np.errstate(all="ignore"):
+        for i in range(len(w)):
+            val = w[i]
+            for k in range(i):
+                val = val - L[i, k] * w[k]
+            w[i] = val * ri[i]
+    return w
+
+
+def _bwd(L, ri, w):
+    w = w.copy()
+    n = len(w)
+    with np.errstate(all="ignore"):
+        for i in range(n - 1, -1, -1):
+            val = w[i]
+            for k in range(i + 1, n):
+                val = val - L[k, i] * w[k]
+            w[i] = val * ri[i]
+    return w
+
+
+def _norm(v):
+    t = F64(0.0)
+    with np.errstate(all="ignore"):
+        for k in range(len(v)):
+            t = t + v[k] * v[k]
+        return np.sqrt(t)
+
+
+def _solve(L, ri, gt):
+    y = _bwd(L, ri, _fwd(L, ri, gt))
+    n = _norm(y)
+    with np.errstate(all="ignore"):
+        wn = _norm(_fwd(L, ri, y / n))
+    return y, n, wn * wn
+
+
+class _Chol:
+    def __init__(self, At, gt, Js):
+        self.At, self.gt = At, gt
+
+    def factor(self, par):
+        self.L, self.ri, ok = _chol(self.At, par)
+        return ok
+
+    def solve(self):
+        return _solve(self.L, self.ri, self.gt)
+
+
+class _QR:
+    """Householder QR of [J D^-1; sqrt(par) I]: R^T R = At + par I without forming At"""
+
+    def __init__(self, At, gt, Js):
+        self.Js, self.gt = Js, gt
+
+    def factor(self, par):
+        p = self.Js.shape[1]
+        with np.errstate(all="ignore"):
+            M = np.concatenate([self.Js, math.sqrt(par) * np.eye(p)]) if par > 0 else self.Js
+            if not np.isfinite(M).all():
+                return False
+            self.R = np.linalg.qr(M, mode="r")
+        d = np.abs(np.diag(self.R))
+        return bool((d > 0).all() and np.isfinite(self.R).all())
+
+    def solve(self):
+        L = self.R.T.copy()
+        with np.errstate(all="ignore"):
+            ri = 1.0 / np.diag(L)
+        return _solve(L, ri, self.gt)
+
+
+def lmpar(fac, gt, delta, par):
+    """MINPACK lmpar in the scaled variables: (y = D p, par); psf_ref.lmpar for any p"""
+    par_lower = F64(0.0)
+    with np.errstate(all="ignore"):
+        if fac.factor(0.0):
+            y, dxnorm, phider = fac.solve()
+            fp = dxnorm - delta
+            if fp <= 0.1 * delta:
+                return y, F64(0.0)
+            par_lower = fp / (delta * phider) if phider > 0.0 else F64(0.0)
+        else:
+            dxnorm = fp = F64(np.inf)
+        gnorm = _norm(gt)
+        par_upper = gnorm / delta
+        if par_upper == 0.0:
+            par_upper = DBL_MIN / min(delta, 0.1)
+        if par > par_upper:
+            par = par_upper
+        elif par < par_lower:
+            par = par_lower
+        if par == 0.0:
+            par = gnorm / dxnorm
+        it = 0
+        while True:
+            it += 1
+            if par == 0.0:
+                par = max(0.001 * par_upper, DBL_MIN)
+            if not fac.factor(par):
+                return np.full(len(gt), np.nan), F64(par)
+            y, dxnorm, phider = fac.solve()
+            fp_old = fp
+            fp = dxnorm - delta
+            if abs(fp) <= 0.1 * delta or (par_lower == 0.0 and fp <= fp_old and fp_old < 0.0) or it == MAX_LMPAR:
+                break
+            par_c = fp / (delta * phider)
+            if fp > 0.0:
+                if par > par_lower:
+                    par_lower = par
+            elif fp < 0.0:
+                if par < par_upper:
+                    par_upper = par
+            par = par + par_c if par + par_c > par_lower else par_lower
+    return y, F64(par)
+
+
+def lm(z, init, v):
+    """lmsder as sg_seqpsf.h restates it, p = len(init).  dict(x, ff, iters, bad, trace)"""
+    rng = np.random.default_rng(ULP_SEED) if v["exp"] == "ulp" else None
+    Fac = _QR if v["linalg"] == "qr" else _Chol
+    x = np.array(init, dtype=F64)
+    p = len(x)
+    trace = []
+    with np.errstate(all="ignore"):
+        a, g, ff, J = sums(x, z, v, rng)
+        if not pr._finite(a, g, ff):
+            return dict(x=x, ff=F64(np.nan), iters=0, bad=True, trace=trace)
+        diag = np.sqrt(np.diag(a)).copy()
+        diag[diag == 0.0] = 1.0
+        xn = _norm(diag * x)
+        delta = F64(100.0) if xn == 0.0 else 100.0 * xn
+        par = F64(0.0)
+        first = True
+        iters = 0
+        for outer in range(1, MAX_ITER + 1):
+            iters = outer
+            fnorm = np.sqrt(ff)
+            if fnorm == 0.0:
+                break
+            gt = g / diag
+            At = a / np.outer(diag, diag)
+            fac = Fac(At, gt, J / diag[None, :])
+            accepted = False
+            for inner in range(MAX_INNER):
+                y, par = lmpar(fac, gt, delta, par)
+                pnorm = _norm(y)
+                if not np.isfinite(pnorm):
+                    break
+                step = -(y / diag)
+                xt = x + step
+                if first and pnorm < delta:
+                    delta = pnorm
+                ff1 = resid(xt, z, v, rng)
+                fnorm1 = np.sqrt(ff1)
+                actred = F64(-1.0)
+                if 0.1 * fnorm1 < fnorm:
+                    u = fnorm1 / fnorm
+                    actred = 1.0 - u * u
+                q = F64(0.0)
+                for i in range(p):
+                    r = F64(0.0)
+                    for j in range(p):
+                        r = r + At[i, j] * y[j]
+                    q = q + y[i] * r
+                t1 = np.sqrt(q if q > 0.0 else F64(0.0)) / fnorm
+                t2 = np.sqrt(par) * pnorm / fnorm
+                prered = t1 * t1 + t2 * t2 / 0.5
+                dirder = -(t1 * t1 + t2 * t2)
+                ratio = actred / prered if prered > 0.0 else F64(0.0)
+                if ratio > 0.25:
+                    if par == 0.0 or ratio >= 0.75:
+                        delta = pnorm / 0.5
+                        par = par * 0.5
+                else:
+                    temp = F64(0.5) if actred >= 0.0 else 0.5 * dirder / (dirder + 0.5 * actred)
+                    if 0.1 * fnorm1 >= fnorm or temp < 0.1:
+                        temp = F64(0.1)
+                    delta = temp * min(delta, pnorm / 0.1)
+                    par = par / temp
+                ok = bool(ratio >= 1e-4)
+                trace.append((outer, inner, ok))
+                if ok:
+                    x = xt
+                    a, g, ff, J = sums(x, z, v, rng)
+                    if not pr._finite(a, g, ff):
+                        return dict(x=x, ff=ff, iters=iters, bad=True, trace=trace)
+                    first = False
+                    diag = np.maximum(diag, np.sqrt(np.diag(a)))
+                    accepted = True
+                    break
+            if not accepted:
+                trace.append((outer, "no progress"))
+                break
+            if bool((np.abs(step) < 1e-4 + 1e-4 * np.abs(x)).all()):
+                trace.append((outer, "delta test"))
+                break
+    return dict(x=x, ff=ff, iters=iters, bad=False, trace=trace)
+
+
+# ---------------------------------------------------------------------------- a frame
+
+def clear_record(status):
+    o = dict({k: F64(0.0) for k in FIELDS}, status=status, angle_fitted=0, iters=0, iters_angle=0, area_x=0, area_y=0,
+             ngood=0, bg=F64(0.0), init=np.zeros(6), noangle=np.zeros(6), trace=[], trace_angle=[], swap=False,
+             margins=[])
+    return o
+
+
+def fit_box(box, area_x, area_y, fit_angle=True, norm=65535.0, scales=(1.0, 1.0), variant="base", start=None):
+    """steps 3 to 6 for the box read from the clamped area (area_x, area_y, w, h): the record of
+    sg_seqpsf_frame as a dict, plus trace / trace_angle / swap and `margins`, the (value, threshold) pairs
+    of the comparisons that decide a branch.  start = (ngood, bg, init) computed before, or None."""
+    v = VARIANTS[variant] if isinstance(variant, str) else variant
+    z = np.asarray(box).astype(F64)
+    h, w = z.shape
+    o = clear_record(FIT_NOT_ENOUGH_PIXELS)
+    o["area_x"], o["area_y"] = int(area_x), int(area_y)
+    if start is None:
+        ngood, bg = background(box)
+        start = (ngood, bg, pr.init_literal(box, bg))
+    o["ngood"], o["bg"], o["init"] = start[0], F64(start[1]), start[2]
+    n = w * h
+    if n <= 6:
+        return o
+    with np.errstate(all="ignore"):
+        r6 = lm(z, o["init"], v)
+        o["iters"], o["trace"] = r6["iters"], r6["trace"]
+        if r6["bad"] or not pr._finite(r6["x"], r6["ff"]):
+            o["status"] = FIT_NONFINITE
+            return o
+        x, ff = r6["x"], r6["ff"]
+        o["noangle"] = x.copy()
+        angle = F64(0.0)
+        if fit_angle:
+            o["margins"].append((abs(x[4] - x[5]), EPSILON))
+        if fit_angle and abs(x[4] - x[5]) >= EPSILON:
+            o["angle_fitted"] = 1
+            r7 = lm(z, np.concatenate([x, [0.0]]), v)
+            o["iters_angle"], o["trace_angle"] = r7["iters"], r7["trace"]
+            if r7["bad"] or not pr._finite(r7["x"], r7["ff"]):
+                o["status"] = FIT_NONFINITE
+                return o
+            x, ff = r7["x"], r7["ff"]
+            angle = -x[6] * 180.0 / math.pi
+            for _ in range(MAX_FOLD):
+                o["margins"].append((abs(angle), 90.0))
+                if not abs(angle) > 90.0:
+                    break
+                angle = angle - 90.0 if angle > 0.0 else angle + 90.0
+            if abs(angle) > 90.0:
+                o["status"] = FIT_NONFINITE
+                return o
+        o.update(B=F64(x[0]), A=F64(x[1]), x0=F64(x[2]), y0=F64(x[3]), sx=F64(x[4]), sy=F64(x[5]))
+        o["fwhmx"] = np.sqrt(o["sx"] / 2.0) * pr.FWHM_K
+        o["fwhmy"] = np.sqrt(o["sy"] / 2.0) * pr.FWHM_K
+        o["mag"] = F64(-2.5) * np.log10(flux(z, x[0], v))
+        o["rmse"] = np.sqrt(F64(ff) / F64(n))
+        o["margins"].append((o["sy"] - o["sx"], 0.0))
+        if o["sy"] > o["sx"]:
+            o["swap"] = True
+            o["sx"], o["sy"] = o["sy"], o["sx"]
+            o["fwhmx"], o["fwhmy"] = o["fwhmy"], o["fwhmx"]
+            if o["angle_fitted"] and angle != 0.0:
+                angle = angle - 90.0 if angle > 0.0 else angle + 90.0
+        o["angle"] = F64(angle)
+        o["B"] = o["B"] / F64(norm)
+        o["A"] = o["A"] / F64(norm)
+        o["rmse"] = o["rmse"] / F64(norm)
+        o["xpos"] = o["x0"] + F64(area_x)
+        o["ypos"] = F64(area_y) + F64(h) - o["y0"]
+        o["margins"] += [(o["fwhmx"], 0.0), (o["fwhmy"], 0.0)]
+        if not np.isfinite(o["fwhmx"]) or not np.isfinite(o["fwhmy"]) or o["fwhmx"] <= 0.0 or o["fwhmy"] <= 0.0:
+            o["status"] = FIT_BAD_FWHM
+            return o
+        o["fwhmx"] = o["fwhmx"] * F64(scales[0])
+        o["fwhmy"] = o["fwhmy"] * F64(scales[1])
+        o["status"] = FIT_STAR
+    return o
+
+
+def _half_margin(v):
+    """round_to_int(v) flips where v -+ 0.5 crosses an integer"""
+    t = float(v) + 0.5 if v >= 0.0 else float(v) - 0.5
+    return (abs(t - round(t)), 0.0, max(abs(float(v)), 1.0))
+
+
+def seqpsf(frames, area, framing=ORIGINAL, included=None, reg_shifts=None, fit_angle=True, norm=65535.0,
+           scales=(1.0, 1.0), variant="base", carry=None, starts=None):
+    """the sequence: (records, carried area (x, y)).  frames [N][H][W] in memory order.  A frame without a
+    PSF is reported (the reference aborts and stores nothing); in FOLLOW_STAR the frames after it are
+    NOT_RUN.  starts: a dict the (frame, clamped area) -> (ngood, bg, init) are kept in between variants."""
+    N, H, W = frames.shape
+    x, y, w, h = area
+    if framing == FOLLOW_STAR and carry is not None:
+        x, y = carry
+    out, stopped = [], False
+    for f in range(N):
+        if included is not None and not included[f]:
+            out.append(clear_record(EXCLUDED))
+            continue
+        if stopped:
+            out.append(clear_record(NOT_RUN))
+            continue
+        fx, fy = x, y
+        if framing == REGISTERED:
+            fx, fy = x - int(reg_shifts[0][f]), y + int(reg_shifts[1][f])
+        ca = enforce_area(W, H, (fx, fy, w, h))
+        box = box_of(frames[f], ca)
+        key = (f, ca)
+        start = None if starts is None else starts.get(key)
+        o = fit_box(box, ca[0], ca[1], fit_angle, norm, scales, variant, start)
+        if starts is not None:
+            starts[key] = (o["ngood"], o["bg"], o["init"])
+        out.append(o)
+        if framing == FOLLOW_STAR:
+            if o["status"] == FIT_STAR:
+                o["margins"] += [_half_margin(o["xpos"]), _half_margin(o["ypos"])]
+                x = round_to_int(float(o["xpos"])) - w // 2
+                y = round_to_int(float(o["ypos"])) - h // 2
+            else:
+                stopped = True
+    return out, (x, y)
+
+
+def shifts(records, ref_image=0):
+    """register_shift_fwhm :424-489 from the records: (rc, shiftx, shifty, fwhm, best index, best fwhm);
+    rc = 1: seqpsf aborted; rc = -1: the reference frame is excluded"""
+    n = len(records)
+    if any(r["status"] not in (FIT_STAR, EXCLUDED) for r in records):
+        return 1, None, None, None, None, None
+    ref = 0 if ref_image < 0 else ref_image
+    if records[ref]["status"] == EXCLUDED:
+        return -1, None, None, None, None, None
+    sx, sy, fw = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=F64)
+    fmin, fidx = float(records[ref]["fwhmx"]), ref
+    for f, r in enumerate(records):
+        if r["status"] == EXCLUDED:
+            continue
+        fw[f] = float(r["fwhmx"])
+        if f == ref:
+            continue
+        if fw[f] < fmin and fw[f] > 0.0:
+            fmin, fidx = fw[f], f
+        sx[f] = round_to_int(float(records[ref]["xpos"]) - float(r["xpos"]))
+        sy[f] = round_to_int(float(r["ypos"]) - float(records[ref]["ypos"]))
+    return 0, sx, sy, fw, fidx, fmin
+
+
+def shift_margins(records, ref_image=0):
+    """the round_to_int arguments of step 8 per frame, as margins"""
+    ref = records[0 if ref_image < 0 else ref_image]
+    out = []
+    for r in records:
+        if r["status"] != FIT_STAR or ref["status"] != FIT_STAR or r is ref:
+            out.append([])
+        else:
+            out.append([_half_margin(float(ref["xpos"]) - float(r["xpos"])), _half_margin(float(r["ypos"]) - float(ref["ypos"]))])
+    return out
+
+
+# ---------------------------------------------------------------------------- stability
+
+def _far(m, tol):
+    val, thr = float(m[0]), float(m[1])
+    den = m[2] if len(m) > 2 else max(abs(val), abs(thr), 1.0)
+    return not np.isfinite(val) or abs(val - thr) > 100.0 * tol * den
+
+
+def classify(outs, tol, extra=()):
+    """outs: {variant: record} of one frame.  (stable, spread)"""
+    base = outs["base"]
+    same = all(all(o[k] == base[k] for k in INT_FIELDS + ("trace", "trace_angle", "swap")) for o in outs.values())
+    if not same or not all(_far(m, tol) for m in list(base["margins"]) + list(extra)):
+        return False, 0.0
+    spread = 0.0
+    if base["status"] in (FIT_STAR, FIT_BAD_FWHM, FIT_NONFINITE):
+        rows = [np.concatenate([[float(o[k]) for k in FIELDS], o["noangle"]]) for o in outs.values()]
+        vals = np.array(rows)
+        for c in range(vals.shape[1]):
+            col = vals[:, c]
+            if not np.isfinite(col).all():
+                if not (np.isnan(col).all() or (col == col[0]).all()):
+                    return False, 0.0
+                continue
+            spread = max(spread, float((col.max() - col.min()) / max(np.abs(col).max(), 1.0)))
+    return True, spread
+
+
+# ---------------------------------------------------------------------------- frames and cases
+# (shared by tests/test_seqpsf_cpu.py, which holds the conditions the GPU tests rely on, and
+# tests/test_gpu_seqpsf.py; smoke() uses the first case)
+
+def render(H, W, stars, seed, bg=800.0, noise=12.0):
+    """a frame in memory order: stars = (x, y, amplitude, fwhm along the major axis, along the minor
+    axis, angle in degrees of the major axis from +x towards +y) in display coordinates, on a seeded
+    normal background"""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W].astype(F64)
+    img = rng.normal(bg, noise, size=(H, W)) if noise > 0 else np.full((H, W), bg)
+    for cx, cy, amp, fa, fb, deg in stars:
+        s1, s2, t = fa / 2.3548, fb / 2.3548, math.radians(deg)
+        u = math.cos(t) * (xx - cx) + math.sin(t) * (yy - cy)
+        vv = -math.sin(t) * (xx - cx) + math.cos(t) * (yy - cy)
+        img = img + amp * np.exp(-(u * u / (2 * s1 * s1) + vv * vv / (2 * s2 * s2)))
+    top = np.clip(np.rint(img), 0, 65535).astype(np.uint16)
+    return np.ascontiguousarray(top[::-1])
+
+
+def sequence(n, H, W, star, seed, drift=(0.0, 0.0), jitter=0.3, **kw):
+    """n frames of one star that moves by drift per frame plus a seeded jitter"""
+    rng = np.random.default_rng(seed + 1000)
+    out = []
+    for f in range(n):
+        jx, jy = rng.uniform(-jitter, jitter, size=2) if jitter > 0 else (0.0, 0.0)
+        s = (star[0] + f * drift[0] + jx, star[1] + f * drift[1] + jy) + tuple(star[2:])
+        out.append(render(H, W, [s], seed + f, **kw))
+    return np.stack(out)
+
+
+H0, W0 = 48, 64
+ELONG = (30.3, 22.6, 20000.0, 5.5, 3.2)        # x, y, amplitude, fwhm major, fwhm minor
+
+
+def _case_frames(name):
+    if name == "elong30":
+        return sequence(6, H0, W0, ELONG + (30.0,), 101)
+    if name == "elong-60":
+        return sequence(6, H0, W0, ELONG + (-60.0,), 102)
+    if name == "round":      # little noise: |SX - SY| stays well below 0.01 and well above rounding
+        return sequence(5, H0, W0, (30.2, 22.4, 20000.0, 3.5, 3.5, 0.0), 103, noise=1.0)
+    if name == "big":        # 160 x 144, two equal plateaus of the filtered box 80 rows apart
+        fr = sequence(5, 144, 160, (80.2, 70.4, 20000.0, 9.0, 6.0, 20.0), 104)
+        for f in range(len(fr)):
+            for ytop in (30, 110):          # display rows; in the 128 x 128 area at (16, 8): box rows 106 and 26
+                fr[f, 144 - 1 - ytop - 2:144 - 1 - ytop + 3, 40:45] = 50000
+        return fr
+    if name == "zeros":      # more than half of the area zero
+        fr = sequence(5, H0, W0, ELONG + (30.0,), 105)
+        fr[:, :, :30] = 0
+        return fr
+    if name == "saturated":
+        return sequence(5, H0, W0, (30.3, 22.6, 400000.0, 5.5, 3.2, 30.0), 106)
+    if name == "blank":
+        return np.zeros((5, H0, W0), dtype=np.uint16)
+    if name == "grid":       # eight stars near the sides and corners
+        stars = [(x, y, 15000.0 + 500 * i, 4.5, 3.0, 25.0) for i, (x, y) in enumerate(
+            [(7.3, 6.6), (32.2, 6.4), (56.7, 6.5), (7.4, 24.3), (56.6, 24.2), (7.2, 41.4), (32.3, 41.6), (56.8, 41.5)])]
+        return np.stack([render(H0, W0, stars, 107 + f) for f in range(5)])
+    if name == "registered":  # the star of frame f sits at (30.3 - sx[f], 22.6 + sy[f])
+        fr = []
+        for f, (sx, sy) in enumerate(zip(*REG_SHIFTS)):
+            fr.append(render(H0, W0, [(30.3 - sx, 22.6 + sy) + ELONG[2:] + (30.0,)], 108 + f))
+        return np.stack(fr)
+    if name == "drift":      # 3 px per frame over 9 frames
+        return sequence(9, H0, W0, (14.3, 20.6) + ELONG[2:] + (30.0,), 109, drift=(3.0, 0.5))
+    if name == "static":
+        return sequence(7, H0, W0, ELONG + (30.0,), 110, jitter=0.0)
+    if name == "edge":       # drifts onto the right edge
+        return sequence(7, H0, W0, (44.3, 22.6) + ELONG[2:] + (30.0,), 111, drift=(2.5, 0.0))
+    if name == "blankmid":   # frame 4 is blank
+        fr = sequence(7, H0, W0, (24.3, 22.6) + ELONG[2:] + (30.0,), 112, drift=(1.5, 0.0))
+        fr[4] = 0
+        return fr
+    raise KeyError(name)
+
+
+REG_SHIFTS = ([0, 3, -4, 2, -30, 1], [0, -2, 3, -3, 1, 20])     # frames 4 and 5: the area leaves the image
+SKIP_1 = [1, 0, 1, 1, 1, 1, 1, 1, 1]
+AREA = (23, 15, 15, 15)
+
+# name -> dict(frames, area, framing, and what else seqpsf takes); the parallel framings first
+CASES = {
+    "a15x11": dict(frames="elong30", area=(23, 17, 15, 11)),
+    "a11x15": dict(frames="elong30", area=(25, 15, 11, 15)),
+    "a7x1": dict(frames="elong30", area=(27, 22, 7, 1)),
+    "a1x7": dict(frames="elong30", area=(30, 19, 1, 7)),
+    "a3x2": dict(frames="elong30", area=(29, 22, 3, 2)),
+    "a7x5": dict(frames="elong30", area=(27, 20, 7, 5)),              # below one wave
+    "big": dict(frames="big", area=(16, 8, 128, 128)),
+    "plus30": dict(frames="elong30", area=AREA),
+    "minus60": dict(frames="elong-60", area=AREA),
+    "round": dict(frames="round", area=(24, 16, 13, 13)),
+    "noangle": dict(frames="elong30", area=AREA, fit_angle=False),
+    "zeros": dict(frames="zeros", area=(18, 15, 22, 15)),
+    "saturated": dict(frames="saturated", area=AREA),
+    "blank": dict(frames="blank", area=AREA),
+    "registered": dict(frames="registered", area=AREA, framing=REGISTERED, reg_shifts=REG_SHIFTS),
+    "drift_original": dict(frames="drift", area=(7, 13, 15, 15)),
+    "drift_follow": dict(frames="drift", area=(7, 13, 15, 15), framing=FOLLOW_STAR, included=SKIP_1),
+    "static_original": dict(frames="static", area=(24, 16, 15, 15), included=[1, 1, 0, 1, 1, 1, 1]),
+    "static_follow": dict(frames="static", area=(24, 16, 15, 15), framing=FOLLOW_STAR, included=[1, 1, 0, 1, 1, 1, 1]),
+    "edge_follow": dict(frames="edge", area=(37, 15, 15, 15), framing=FOLLOW_STAR, included=[1, 1, 1, 0, 1, 1, 1]),
+    "blankmid_follow": dict(frames="blankmid", area=(17, 15, 15, 15), framing=FOLLOW_STAR, included=[1, 0, 1, 1, 1, 1, 1]),
+}
+# the clamping cases: the area given partly outside each side and corner of the grid frame
+for _i, _a in enumerate([(-4, -3), (25, -5), (53, -2), (-6, 17), (55, 18), (-2, 37), (24, 40), (52, 38)]):
+    CASES["clamp%d" % _i] = dict(frames="grid", area=_a + (15, 13))
+
+_frames, _results = {}, {}
+
+
+def case_frames(name):
+    key = CASES[name]["frames"]
+    if key not in _frames:
+        _frames[key] = _case_frames(key)
+        _frames[key].setflags(write=False)
+    return _frames[key]
+
+
+def case(name, tol=None):
+    """the case's frames, seqpsf arguments and result, computed once: dict(frames, args, records (base),
+    carry, stable [N] bool, spread, shifts = shifts(records, 0))"""
+    tol = TOL if tol is None else tol
+    if (name, tol) in _results:
+        return _results[(name, tol)]
+    c = dict(CASES[name])
+    frames = case_frames(name)
+    c.pop("frames")
+    area = c.pop("area")
+    starts = {}
+    runs = {v: seqpsf(frames, area, variant=v, starts=starts, **c) for v in ALL_VARIANTS}
+    records, carry = runs["base"]
+    sm = shift_margins(records, 0) if shifts(records, 0)[0] == 0 else [[] for _ in records]
+    stable, spread = [], 0.0
+    for f in range(len(records)):
+        st, sp = classify({v: runs[v][0][f] for v in ALL_VARIANTS}, tol, sm[f])
+        stable.append(st)
+        if st:
+            spread = max(spread, sp)
+    res = dict(frames=frames, area=area, args=c, records=records, carry=carry, stable=np.array(stable), spread=spread,
+               shifts=shifts(records, 0))
+    _results[(name, tol)] = res
+    return res
