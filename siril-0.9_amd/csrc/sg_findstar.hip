@@ -299,25 +299,29 @@ __device__ static inline double sgs_wave_sum(double v) {
 struct SgPsfWaveEval {
 	const uint16_t *box;
 	int n2, ne, lane;
-	__device__ void full(const double x[SGP_NP], SgPsfSums &s) const {
-		sgp_sums_zero(s);
+	template <int NP>
+	__device__ void full(const double *x, SgPsfSums<NP> &s) const {
+		sgp_sums_zero<NP>(s);
+		const SgPsfModel<NP> m = sgp_model<NP>(x);
 		for (int p = lane; p < ne; p += 64) {
 			const int i = p / n2, j = p - i * n2;
-			sgp_pixel(x, (double)(j + 1), (double)(i + 1), (double)box[p], s);
+			sgp_pixel<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[p], s);
 		}
 #pragma unroll
-		for (int k = 0; k < 21; k++)
+		for (int k = 0; k < NP * (NP + 1) / 2; k++)
 			s.a[k] = sgs_wave_sum(s.a[k]);
 #pragma unroll
-		for (int k = 0; k < SGP_NP; k++)
+		for (int k = 0; k < NP; k++)
 			s.g[k] = sgs_wave_sum(s.g[k]);
 		s.ff = sgs_wave_sum(s.ff);
 	}
-	__device__ double resid(const double x[SGP_NP]) const {
+	template <int NP>
+	__device__ double resid(const double *x) const {
+		const SgPsfModel<NP> m = sgp_model<NP>(x);
 		double ff = 0.;
 		for (int p = lane; p < ne; p += 64) {
 			const int i = p / n2, j = p - i * n2;
-			const double r = sgp_resid(x, (double)(j + 1), (double)(i + 1), (double)box[p]);
+			const double r = sgp_resid<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[p]);
 			ff += r * r;
 		}
 		return sgs_wave_sum(ff);
@@ -377,7 +381,7 @@ __global__ void __launch_bounds__(64 * SGS_WAVES) SGS_OCC_ATTR k_starfit_fit(SgF
 	}
 	const int best = 65535 - (int)(key & 0xFFFFu);
 	double init[SGP_NP];
-	sgp_init_walks(box, n2, p.bg[f], best / n2, best % n2, (uint16_t)(key >> 16), init);
+	sgp_init_walks(box, n2, n2, p.bg[f], best / n2, best % n2, (uint16_t)(key >> 16), init);
 	SgPsfWaveEval ev = {box, n2, ne, lane};
 	SgPsfFit o;
 	sgp_fit(ev, init, n2, cx, cy, p.norm, p.scale_x, p.scale_y, p.roundness, o);

@@ -1,14 +1,17 @@
 /*
- * sg_psf.h - the per-box part of peaker (src/algos/star_finder.c:200-247, src/algos/PSF.c:46-157,
- * 160-220, 314-428, 620-662), host + device, no HIP types: the start values of psf_init_data, the
- * model and Jacobian of psf_Gaussian_f / _df as sums, the Levenberg-Marquardt iteration of GSL's
- * lmsder (MINPACK lmder / lmpar) restated on the 6 x 6 normal equations, the finish of
- * psf_minimiz_no_angle / psf_global_minimisation, psf_update_units as two factors, is_star, and
- * sg_psf_fit_box, which runs a whole box sequentially.  k_starfit_fit (sg_findstar.hip) calls the
- * same functions with a lane-parallel evaluator, so everything but its sums is checked on the host
+ * sg_psf.h - the PSF fit of peaker (src/algos/star_finder.c:200-247) and of seqpsf, host + device,
+ * no HIP types (src/algos/PSF.c:46-157, 160-309, 314-428, 620-662): the start values of
+ * psf_init_data on an h x w box, the models and Jacobians of psf_Gaussian_f / _df (p = 6) and
+ * psf_Gaussian_f_an / _df_an (p = 7) as sums, the Levenberg-Marquardt iteration of GSL's lmsder
+ * (MINPACK lmder / lmpar) restated on the p x p normal equations, and the sequential evaluator.
+ * All of it is written once, with the parameter count NP as a template argument; sg_seqpsf.h adds
+ * what belongs to seqpsf alone.  Then peaker's own part: the finish of psf_minimiz_no_angle /
+ * psf_global_minimisation, psf_update_units as two factors, is_star, and sg_psf_fit_box, which runs
+ * a whole box sequentially.  k_starfit_fit (sg_findstar.hip) calls the same functions with a
+ * lane-parallel evaluator, so everything but its sums is checked on the host
  * (tests/test_psf_cpu.py).
  *
- * The box is the gsl_matrix z of peaker as uint16, z[i][j] = box[i * n2 + j] with n2 = 2r: rows run
+ * peaker's box is its gsl_matrix z as uint16, z[i][j] = box[i * n2 + j] with n2 = 2r: rows run
  * along image x, and the model's x0 belongs to the column index j (image y).  Kept as it is.
  *
  * The solver works on S = (J^T J, J^T f, |f|^2), never on J itself, and in the scaled variables
@@ -19,6 +22,9 @@
  * positive (rank-deficient J, or a value that is not finite) takes lmpar's rank-deficient branch:
  * no Newton step, lower bound 0.
  * Every loop has a constant bound: 10 outer iterations, 10 trial steps each, 10 lmpar refinements.
+ *
+ * An evaluator gives ev.full<NP>(x, sums), the sums at x, ev.resid<NP>(x), |f(x)|^2, and
+ * ev.flux(B), the sum of z - B.
  */
 #pragma once
 #include <math.h>
@@ -33,29 +39,36 @@
 #define SGP_HD static inline
 #define SGP_HD_MEMBER inline
 #endif
-/* the 6 x 6 loops are unrolled on the device so that their arrays stay in registers */
+/* the NP x NP loops are unrolled on the device so that their arrays stay in registers */
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SGP_UNROLL _Pragma("unroll")
 #else
 #define SGP_UNROLL
 #endif
 
-#define SGP_NP 6			/* B, A, x0, y0, SX, SY */
-#define SGP_MAX_ITER 10			/* MAX_ITER_NO_ANGLE */
+#define SGP_NP 6			/* B, A, x0, y0, SX, SY; the angle fit adds alpha */
+#define SGP_MAX_ITER 10			/* MAX_ITER_NO_ANGLE = MAX_ITER_ANGLE */
 #define SGP_MAX_INNER 10		/* lmsder's trial steps per iteration */
 #define SGP_MAX_LMPAR 10
 #define SGP_LN2 0.6931471805599453	/* log(2.0) */
 #define SGP_FWHM_K 2.3548200450309493	/* 2 * sqrt(log(2.) * 2) */
 
-/* J^T J (upper triangle, row-major: (0,0) (0,1) .. (0,5) (1,1) ..), J^T f and |f|^2 */
+/* ---------------------------------------------------------------- the models as sums */
+
+/* J^T J (upper triangle, row-major: (0,0) (0,1) .. (0,NP-1) (1,1) ..), J^T f and |f|^2:
+ * 21 + 6 + 1 or 28 + 7 + 1 doubles */
+template <int NP>
 struct SgPsfSums {
-	double a[21], g[SGP_NP], ff;
+	double a[NP * (NP + 1) / 2], g[NP], ff;
 };
 
-SGP_HD void sgp_sums_zero(SgPsfSums &s) {
-	for (int k = 0; k < 21; k++)
+template <int NP>
+SGP_HD void sgp_sums_zero(SgPsfSums<NP> &s) {
+SGP_UNROLL
+	for (int k = 0; k < NP * (NP + 1) / 2; k++)
 		s.a[k] = 0.;
-	for (int k = 0; k < SGP_NP; k++)
+SGP_UNROLL
+	for (int k = 0; k < NP; k++)
 		s.g[k] = 0.;
 	s.ff = 0.;
 }
@@ -64,50 +77,110 @@ SGP_HD int sgp_finite(double v) {
 	return v - v == 0.;
 }
 
-SGP_HD int sgp_sums_finite(const SgPsfSums &s) {
+template <int NP>
+SGP_HD int sgp_sums_finite(const SgPsfSums<NP> &s) {
 	double t = s.ff;
-	for (int k = 0; k < 21; k++)
+SGP_UNROLL
+	for (int k = 0; k < NP * (NP + 1) / 2; k++)
 		t += s.a[k];
-	for (int k = 0; k < SGP_NP; k++)
+SGP_UNROLL
+	for (int k = 0; k < NP; k++)
 		t += s.g[k];
 	return sgp_finite(t);
 }
 
-/* psf_Gaussian_f at pixel (row i, column j) of value z: the residual, tx = j + 1, ty = i + 1 */
-SGP_HD double sgp_resid(const double x[SGP_NP], double tx, double ty, double z) {
-	const double dx = tx - x[2], dy = ty - x[3];
-	const double c = exp(-(dx * dx / x[4] + dy * dy / x[5]));
-	return x[0] + x[1] * c - z;
-}
-
-/* psf_Gaussian_f and psf_Gaussian_df (sigma = 1) at one pixel, added to the sums; one exp */
-SGP_HD void sgp_pixel(const double x[SGP_NP], double tx, double ty, double z, SgPsfSums &s) {
-	const double dx = tx - x[2], dy = ty - x[3];
-	const double c = exp(-(dx * dx / x[4] + dy * dy / x[5]));
-	const double r = x[0] + x[1] * c - z;
-	double J[SGP_NP];
-	J[0] = 1.;
-	J[1] = c;
-	J[2] = x[1] * c * 2 * dx / x[4];
-	J[3] = x[1] * c * 2 * dy / x[5];
-	J[4] = x[1] * c * (dx * dx) / (x[4] * x[4]);
-	J[5] = x[1] * c * (dy * dy) / (x[5] * x[5]);
+/* a pixel's residual r and Jacobian row J added to the sums */
+template <int NP>
+SGP_HD void sgp_accum(const double J[NP], double r, SgPsfSums<NP> &s) {
 	int k = 0;
 SGP_UNROLL
-	for (int i = 0; i < SGP_NP; i++) {
+	for (int i = 0; i < NP; i++) {
 SGP_UNROLL
-		for (int j = i; j < SGP_NP; j++)
+		for (int j = i; j < NP; j++)
 			s.a[k++] += J[i] * J[j];
 		s.g[i] += J[i] * r;
 	}
 	s.ff += r * r;
 }
 
+/* what a model evaluation at x shares among its pixels: cos and sin of alpha for p = 7 */
+template <int NP>
+struct SgPsfModel {
+	double ca, sa;
+};
+
+template <int NP>
+SGP_HD SgPsfModel<NP> sgp_model(const double x[NP]) {
+	SgPsfModel<NP> m;
+	if (NP == 7) {
+		m.ca = cos(x[NP - 1]);
+		m.sa = sin(x[NP - 1]);
+	} else {
+		m.ca = 1.;
+		m.sa = 0.;
+	}
+	return m;
+}
+
+/* the residual at pixel (row i, column j) of value z: tx = j + 1, ty = i + 1.  p = 6:
+ * psf_Gaussian_f; p = 7: psf_Gaussian_f_an as written (tmpx = cos a (j + 1 - x0) - sin a (i + 1 - y0)
+ * + x0, then tmpx - x0 again) */
+template <int NP>
+SGP_HD double sgp_resid(const double x[NP], const SgPsfModel<NP> &m, double tx, double ty, double z) {
+	double dx, dy;
+	if (NP == 7) {
+		const double tmpx = m.ca * (tx - x[2]) - m.sa * (ty - x[3]) + x[2];
+		const double tmpy = m.sa * (tx - x[2]) + m.ca * (ty - x[3]) + x[3];
+		dx = tmpx - x[2];
+		dy = tmpy - x[3];
+	} else {
+		dx = tx - x[2];
+		dy = ty - x[3];
+	}
+	const double c = exp(-(dx * dx / x[4] + dy * dy / x[5]));
+	return x[0] + x[1] * c - z;
+}
+
+/* residual and Jacobian row (sigma = 1) at one pixel, added to the sums; one exp.  p = 6:
+ * psf_Gaussian_df; p = 7 is psf_Gaussian_df_an literally: columns 2 and 3 keep their cos(alpha)
+ * factor (the derivative with respect to x0 / y0 of the rotated coordinates is not that, the
+ * reference's formula is the contract), column 6 as written */
+template <int NP>
+SGP_HD void sgp_pixel(const double x[NP], const SgPsfModel<NP> &m, double tx, double ty, double z, SgPsfSums<NP> &s) {
+	double J[NP], dx, dy;
+	if (NP == 7) {
+		const double tmpx = m.ca * (tx - x[2]) - m.sa * (ty - x[3]) + x[2];
+		const double tmpy = m.sa * (tx - x[2]) + m.ca * (ty - x[3]) + x[3];
+		dx = tmpx - x[2];
+		dy = tmpy - x[3];
+	} else {
+		dx = tx - x[2];
+		dy = ty - x[3];
+	}
+	const double c = exp(-(dx * dx / x[4] + dy * dy / x[5]));
+	const double r = x[0] + x[1] * c - z;
+	J[0] = 1.;
+	J[1] = c;
+	J[2] = x[1] * c * 2 * dx / x[4];
+	J[3] = x[1] * c * 2 * dy / x[5];
+	J[4] = x[1] * c * (dx * dx) / (x[4] * x[4]);
+	J[5] = x[1] * c * (dy * dy) / (x[5] * x[5]);
+	if (NP == 7) {
+		J[2] = J[2] * m.ca;
+		J[3] = J[3] * m.ca;
+		const double derx = -m.sa * (tx - x[2]) - m.ca * (ty - x[3]);
+		const double dery = m.ca * (tx - x[2]) - m.sa * (ty - x[3]);
+		J[NP - 1] = -x[1] * c * (2 * dx / x[4] * derx + 2 * dy / x[5] * dery);
+	}
+	sgp_accum<NP>(J, r, s);
+}
+
 /* ---------------------------------------------------------------- start values (psf_init_data) */
 
-/* getMedian3x3 of the box at (row i, column j): the neighbours inside the box sorted together with
- * zero padding, read from the offset 8 - n - 1: the mean of the 3rd and 4th smallest of 8, the 2nd
- * smallest of 5, the smallest of 3; truncated to WORD */
+/* getMedian3x3 of a 2r x 2r box at (row i, column j): the neighbours inside the box sorted together
+ * with zero padding, read from the offset 8 - n - 1: the mean of the 3rd and 4th smallest of 8, the
+ * 2nd smallest of 5, the smallest of 3; truncated to WORD.
+ * Not shared with sq_median3x3 (n = 1 and 2 too): that one makes k_starfit_fit's code longer. */
 SGP_HD uint16_t sgp_median3x3(const uint16_t *box, int n2, int i, int j) {
 	uint32_t v[8];
 	int n = 0;
@@ -138,18 +211,18 @@ SGP_UNROLL
 }
 
 /* the four half-maximum walks from the maximum (row mi, column mj, filtered value mx) on the
- * UNFILTERED box against bg, and x_init = {bg, max, (jj1 + jj2 + 2) / 2, (ii1 + ii2 + 2) / 2,
+ * UNFILTERED h x w box against bg, and x_init = {bg, max, (jj1 + jj2 + 2) / 2, (ii1 + ii2 + 2) / 2,
  * (size_t)(SQR(jj1 - jj2) / 4 / log 2), (size_t)(SQR(ii1 - ii2) / 4 / log 2)} */
-SGP_HD void sgp_init_walks(const uint16_t *box, int n2, double bg, int mi, int mj, uint16_t mx, double init[SGP_NP]) {
-	const double zc = (double)box[mi * n2 + mj] - bg;
+SGP_HD void sgp_init_walks(const uint16_t *box, int h, int w, double bg, int mi, int mj, uint16_t mx, double init[SGP_NP]) {
+	const double zc = (double)box[mi * w + mj] - bg;
 	int ii1 = mi, ii2 = mi, jj1 = mj, jj2 = mj;
-	while (2.0 * ((double)box[ii1 * n2 + mj] - bg) > zc && ii1 < n2 - 1)
+	while (2.0 * ((double)box[ii1 * w + mj] - bg) > zc && ii1 < h - 1)
 		ii1++;
-	while (2.0 * ((double)box[ii2 * n2 + mj] - bg) > zc && ii2 > 0)
+	while (2.0 * ((double)box[ii2 * w + mj] - bg) > zc && ii2 > 0)
 		ii2--;
-	while (2.0 * ((double)box[mi * n2 + jj1] - bg) > zc && jj1 < n2 - 1)
+	while (2.0 * ((double)box[mi * w + jj1] - bg) > zc && jj1 < w - 1)
 		jj1++;
-	while (2.0 * ((double)box[mi * n2 + jj2] - bg) > zc && jj2 > 0)
+	while (2.0 * ((double)box[mi * w + jj2] - bg) > zc && jj2 > 0)
 		jj2--;
 	const double di = (double)((ii1 - ii2) * (ii1 - ii2)), dj = (double)((jj1 - jj2) * (jj1 - jj2));
 	init[0] = bg;
@@ -160,30 +233,33 @@ SGP_HD void sgp_init_walks(const uint16_t *box, int n2, double bg, int mi, int m
 	init[5] = (double)(uint64_t)(di / 4.0 / SGP_LN2);
 }
 
-/* psf_init_data, sequentially: the first maximum of the median-filtered box in row-major order */
-SGP_HD void sgp_init_box(const uint16_t *box, int n2, double bg, double init[SGP_NP]) {
+/* psf_init_data, sequentially: the first maximum of the median-filtered box in row-major order;
+ * median(box, i, j) is the box's getMedian3x3 */
+template <class Median>
+static inline void sgp_init_box(const uint16_t *box, int h, int w, double bg, Median median, double init[SGP_NP]) {
 	int best = 0;
 	uint16_t mx = 0;
-	for (int p = 0; p < n2 * n2; p++) {
-		const uint16_t m = sgp_median3x3(box, n2, p / n2, p % n2);
+	for (int p = 0; p < h * w; p++) {
+		const uint16_t m = median(box, p / w, p % w);
 		if (p == 0 || m > mx) {
 			mx = m;
 			best = p;
 		}
 	}
-	sgp_init_walks(box, n2, bg, best / n2, best % n2, mx, init);
+	sgp_init_walks(box, h, w, bg, best / w, best % w, mx, init);
 }
 
-/* ---------------------------------------------------------------- 6 x 6 linear algebra */
+/* ---------------------------------------------------------------- NP x NP linear algebra */
 
-/* L L^T = At + par I, ri[j] = 1 / L[j][j] (the solves multiply by it: six divisions a
- * factorisation instead of fifteen, none in a solve); 0 when a pivot is not positive */
-SGP_HD int sgp_chol(const double At[SGP_NP][SGP_NP], double par, double L[SGP_NP][SGP_NP], double ri[SGP_NP]) {
+/* L L^T = At + par I, ri[j] = 1 / L[j][j] (the solves multiply by it: NP divisions a
+ * factorisation instead of NP (NP - 1) / 2, none in a solve); 0 when a pivot is not positive */
+template <int NP>
+SGP_HD int sgp_chol(const double At[NP][NP], double par, double L[NP][NP], double ri[NP]) {
 	int ok = 1;
-	SGP_UNROLL
-	for (int j = 0; j < SGP_NP; j++) {
+SGP_UNROLL
+	for (int j = 0; j < NP; j++) {
 		double d = At[j][j] + par;
-		SGP_UNROLL
+SGP_UNROLL
 		for (int k = 0; k < j; k++)
 			d -= L[j][k] * L[j][k];
 		if (!(d > 0.))
@@ -191,10 +267,10 @@ SGP_HD int sgp_chol(const double At[SGP_NP][SGP_NP], double par, double L[SGP_NP
 		const double l = sqrt(d), rl = 1. / l;
 		L[j][j] = l;
 		ri[j] = rl;
-		SGP_UNROLL
-		for (int i = j + 1; i < SGP_NP; i++) {
+SGP_UNROLL
+		for (int i = j + 1; i < NP; i++) {
 			double v = At[i][j];
-			SGP_UNROLL
+SGP_UNROLL
 			for (int k = 0; k < j; k++)
 				v -= L[i][k] * L[j][k];
 			L[i][j] = v * rl;
@@ -204,11 +280,12 @@ SGP_HD int sgp_chol(const double At[SGP_NP][SGP_NP], double par, double L[SGP_NP
 }
 
 /* w <- L^-1 w */
-SGP_HD void sgp_fwd(const double L[SGP_NP][SGP_NP], const double ri[SGP_NP], double w[SGP_NP]) {
-	SGP_UNROLL
-	for (int i = 0; i < SGP_NP; i++) {
+template <int NP>
+SGP_HD void sgp_fwd(const double L[NP][NP], const double ri[NP], double w[NP]) {
+SGP_UNROLL
+	for (int i = 0; i < NP; i++) {
 		double v = w[i];
-		SGP_UNROLL
+SGP_UNROLL
 		for (int k = 0; k < i; k++)
 			v -= L[i][k] * w[k];
 		w[i] = v * ri[i];
@@ -216,52 +293,54 @@ SGP_HD void sgp_fwd(const double L[SGP_NP][SGP_NP], const double ri[SGP_NP], dou
 }
 
 /* w <- L^-T w */
-SGP_HD void sgp_bwd(const double L[SGP_NP][SGP_NP], const double ri[SGP_NP], double w[SGP_NP]) {
-	SGP_UNROLL
-	for (int i = SGP_NP - 1; i >= 0; i--) {
+template <int NP>
+SGP_HD void sgp_bwd(const double L[NP][NP], const double ri[NP], double w[NP]) {
+SGP_UNROLL
+	for (int i = NP - 1; i >= 0; i--) {
 		double v = w[i];
-		SGP_UNROLL
-		for (int k = i + 1; k < SGP_NP; k++)
+SGP_UNROLL
+		for (int k = i + 1; k < NP; k++)
 			v -= L[k][i] * w[k];
 		w[i] = v * ri[i];
 	}
 }
 
-SGP_HD double sgp_norm6(const double v[SGP_NP]) {
+template <int NP>
+SGP_HD double sgp_norm(const double v[NP]) {
 	double t = 0.;
-	SGP_UNROLL
-	for (int k = 0; k < SGP_NP; k++)
+SGP_UNROLL
+	for (int k = 0; k < NP; k++)
 		t += v[k] * v[k];
 	return sqrt(t);
 }
 
 /* y = (At + par I)^-1 gt through L; |L^-1 (y / |y|)|^2 in *phider.  Returns |y|. */
-SGP_HD double sgp_solve(const double L[SGP_NP][SGP_NP], const double ri[SGP_NP], const double gt[SGP_NP], double y[SGP_NP],
-		double *phider) {
-	SGP_UNROLL
-	for (int k = 0; k < SGP_NP; k++)
+template <int NP>
+SGP_HD double sgp_solve(const double L[NP][NP], const double ri[NP], const double gt[NP], double y[NP], double *phider) {
+SGP_UNROLL
+	for (int k = 0; k < NP; k++)
 		y[k] = gt[k];
-	sgp_fwd(L, ri, y);
-	sgp_bwd(L, ri, y);
-	const double n = sgp_norm6(y);
-	double w[SGP_NP];
-	SGP_UNROLL
-	for (int k = 0; k < SGP_NP; k++)
+	sgp_fwd<NP>(L, ri, y);
+	sgp_bwd<NP>(L, ri, y);
+	const double n = sgp_norm<NP>(y);
+	double w[NP];
+SGP_UNROLL
+	for (int k = 0; k < NP; k++)
 		w[k] = y[k] / n;
-	sgp_fwd(L, ri, w);
-	const double wn = sgp_norm6(w);
+	sgp_fwd<NP>(L, ri, w);
+	const double wn = sgp_norm<NP>(w);
 	*phider = wn * wn;
 	return n;
 }
 
 /* MINPACK lmpar in the scaled variables: the step y = D p (to be taken downhill, p = -D^-1 y) and
  * the Levenberg-Marquardt parameter for the region |y| <= delta */
-SGP_HD void sgp_lmpar(const double At[SGP_NP][SGP_NP], const double gt[SGP_NP], double delta, double *par_io,
-		double y[SGP_NP]) {
-	double L[SGP_NP][SGP_NP], ri[SGP_NP];
+template <int NP>
+SGP_HD void sgp_lmpar(const double At[NP][NP], const double gt[NP], double delta, double *par_io, double y[NP]) {
+	double L[NP][NP], ri[NP];
 	double par = *par_io, par_lower = 0., phider, dxnorm, fp;
-	if (sgp_chol(At, 0., L, ri)) {
-		dxnorm = sgp_solve(L, ri, gt, y, &phider);	/* the Gauss-Newton step */
+	if (sgp_chol<NP>(At, 0., L, ri)) {
+		dxnorm = sgp_solve<NP>(L, ri, gt, y, &phider);	/* the Gauss-Newton step */
 		fp = dxnorm - delta;
 		if (fp <= 0.1 * delta) {
 			*par_io = 0.;
@@ -272,7 +351,7 @@ SGP_HD void sgp_lmpar(const double At[SGP_NP][SGP_NP], const double gt[SGP_NP], 
 		dxnorm = INFINITY;
 		fp = INFINITY;
 	}
-	const double gnorm = sgp_norm6(gt);
+	const double gnorm = sgp_norm<NP>(gt);
 	double par_upper = gnorm / delta;
 	if (par_upper == 0.)
 		par_upper = DBL_MIN / (delta < 0.1 ? delta : 0.1);
@@ -288,13 +367,13 @@ SGP_HD void sgp_lmpar(const double At[SGP_NP][SGP_NP], const double gt[SGP_NP], 
 			if (par < DBL_MIN)
 				par = DBL_MIN;
 		}
-		if (!sgp_chol(At, par, L, ri)) {	/* not finite: the trial step is refused by its caller */
-			SGP_UNROLL
-			for (int k = 0; k < SGP_NP; k++)
+		if (!sgp_chol<NP>(At, par, L, ri)) {	/* not finite: the trial step is refused by its caller */
+SGP_UNROLL
+			for (int k = 0; k < NP; k++)
 				y[k] = NAN;
 			break;
 		}
-		dxnorm = sgp_solve(L, ri, gt, y, &phider);
+		dxnorm = sgp_solve<NP>(L, ri, gt, y, &phider);
 		const double fp_old = fp;
 		fp = dxnorm - delta;
 		if (fabs(fp) <= 0.1 * delta || (par_lower == 0. && fp <= fp_old && fp_old < 0.) || it == SGP_MAX_LMPAR)
@@ -314,26 +393,26 @@ SGP_HD void sgp_lmpar(const double At[SGP_NP][SGP_NP], const double gt[SGP_NP], 
 
 /* ---------------------------------------------------------------- the fit */
 
-SGP_HD int sgp_tri(int i, int j) {	/* index of (i, j), i <= j, in SgPsfSums::a */
-	return i * SGP_NP - i * (i - 1) / 2 + (j - i);
+SGP_HD int sgp_tri(int np, int i, int j) {	/* index of (i, j), i <= j, in SgPsfSums<np>::a */
+	return i * np - i * (i - 1) / 2 + (j - i);
 }
 
-/* lmsder on an evaluator: ev.full(x, sums) gives the sums at x, ev.resid(x) gives |f(x)|^2.
- * x holds the start values and receives the result; *ff = |f|^2 at the final x; *iters = outer
- * iterations made.  Returns 0, or 1 when a value at an accepted point is not finite. */
-template <class Ev>
-SGP_HD int sgp_lm(Ev &ev, double x[SGP_NP], double *ff_out, int *iters) {
-	SgPsfSums s;
-	double diag[SGP_NP], At[SGP_NP][SGP_NP], gt[SGP_NP], y[SGP_NP], p[SGP_NP], xt[SGP_NP];
+/* lmsder on an evaluator, p = NP.  x holds the start values and receives the result; *ff = |f|^2
+ * at the final x; *iters = outer iterations made.  Returns 0, or 1 when a value at an accepted
+ * point is not finite. */
+template <int NP, class Ev>
+SGP_HD int sgp_lm(Ev &ev, double x[NP], double *ff_out, int *iters) {
+	SgPsfSums<NP> s;
+	double diag[NP], At[NP][NP], gt[NP], y[NP], p[NP], xt[NP];
 	*iters = 0;
 	*ff_out = NAN;
-	ev.full(x, s);
-	if (!sgp_sums_finite(s))
+	ev.template full<NP>(x, s);
+	if (!sgp_sums_finite<NP>(s))
 		return 1;
 	double xn = 0.;
-	SGP_UNROLL
-	for (int k = 0; k < SGP_NP; k++) {
-		diag[k] = sqrt(s.a[sgp_tri(k, k)]);
+SGP_UNROLL
+	for (int k = 0; k < NP; k++) {
+		diag[k] = sqrt(s.a[sgp_tri(NP, k, k)]);
 		if (diag[k] == 0.)
 			diag[k] = 1.;
 		xn += (diag[k] * x[k]) * (diag[k] * x[k]);
@@ -346,38 +425,38 @@ SGP_HD int sgp_lm(Ev &ev, double x[SGP_NP], double *ff_out, int *iters) {
 		const double fnorm = sqrt(ff);
 		if (fnorm == 0.)	/* lmsder returns at once; dx = 0 meets the delta test */
 			break;
-		SGP_UNROLL
-		for (int i = 0; i < SGP_NP; i++) {
+SGP_UNROLL
+		for (int i = 0; i < NP; i++) {
 			gt[i] = s.g[i] / diag[i];
-			SGP_UNROLL
-			for (int j = 0; j < SGP_NP; j++)
-				At[i][j] = s.a[i <= j ? sgp_tri(i, j) : sgp_tri(j, i)] / (diag[i] * diag[j]);
+SGP_UNROLL
+			for (int j = 0; j < NP; j++)
+				At[i][j] = s.a[i <= j ? sgp_tri(NP, i, j) : sgp_tri(NP, j, i)] / (diag[i] * diag[j]);
 		}
 		int accepted = 0;
 		for (int inner = 0; inner < SGP_MAX_INNER && !accepted; inner++) {
-			sgp_lmpar(At, gt, delta, &par, y);
-			const double pnorm = sgp_norm6(y);
+			sgp_lmpar<NP>(At, gt, delta, &par, y);
+			const double pnorm = sgp_norm<NP>(y);
 			if (!sgp_finite(pnorm))
 				break;
-			SGP_UNROLL
-			for (int k = 0; k < SGP_NP; k++) {
+SGP_UNROLL
+			for (int k = 0; k < NP; k++) {
 				p[k] = -(y[k] / diag[k]);
 				xt[k] = x[k] + p[k];
 			}
 			if (first && pnorm < delta)
 				delta = pnorm;
-			const double ff1 = ev.resid(xt), fnorm1 = sqrt(ff1);
+			const double ff1 = ev.template resid<NP>(xt), fnorm1 = sqrt(ff1);
 			double actred = -1.;
 			if (0.1 * fnorm1 < fnorm) {
 				const double u = fnorm1 / fnorm;
 				actred = 1. - u * u;
 			}
 			double q = 0.;	/* |J p|^2 */
-			SGP_UNROLL
-			for (int i = 0; i < SGP_NP; i++) {
+SGP_UNROLL
+			for (int i = 0; i < NP; i++) {
 				double r = 0.;
-				SGP_UNROLL
-				for (int j = 0; j < SGP_NP; j++)
+SGP_UNROLL
+				for (int j = 0; j < NP; j++)
 					r += At[i][j] * y[j];
 				q += y[i] * r;
 			}
@@ -397,17 +476,17 @@ SGP_HD int sgp_lm(Ev &ev, double x[SGP_NP], double *ff_out, int *iters) {
 				par /= temp;
 			}
 			if (ratio >= 1e-4) {
-				SGP_UNROLL
-				for (int k = 0; k < SGP_NP; k++)
+SGP_UNROLL
+				for (int k = 0; k < NP; k++)
 					x[k] = xt[k];
-				ev.full(x, s);
+				ev.template full<NP>(x, s);
 				ff = s.ff;
-				if (!sgp_sums_finite(s))
+				if (!sgp_sums_finite<NP>(s))
 					return 1;
 				first = 0;
-				SGP_UNROLL
-				for (int k = 0; k < SGP_NP; k++) {
-					const double c = sqrt(s.a[sgp_tri(k, k)]);
+SGP_UNROLL
+				for (int k = 0; k < NP; k++) {
+					const double c = sqrt(s.a[sgp_tri(NP, k, k)]);
 					if (c > diag[k])
 						diag[k] = c;
 				}
@@ -417,8 +496,8 @@ SGP_HD int sgp_lm(Ev &ev, double x[SGP_NP], double *ff_out, int *iters) {
 		if (!accepted)	/* "no progress": the fit stops with its current x */
 			break;
 		int conv = 1;	/* gsl_multifit_test_delta(dx, x, 1e-4, 1e-4) */
-		SGP_UNROLL
-		for (int k = 0; k < SGP_NP; k++)
+SGP_UNROLL
+		for (int k = 0; k < NP; k++)
 			if (!(fabs(p[k]) < 1e-4 + 1e-4 * fabs(x[k])))
 				conv = 0;
 		if (conv)
@@ -428,7 +507,38 @@ SGP_HD int sgp_lm(Ev &ev, double x[SGP_NP], double *ff_out, int *iters) {
 	return 0;
 }
 
-/* ---------------------------------------------------------------- finish and is_star */
+/* the sequential evaluator of an h x w box: every sum in matrix order */
+struct SgPsfSeqEval {
+	const uint16_t *box;
+	int h, w;
+	template <int NP>
+	SGP_HD_MEMBER void full(const double *x, SgPsfSums<NP> &s) const {
+		sgp_sums_zero<NP>(s);
+		const SgPsfModel<NP> m = sgp_model<NP>(x);
+		for (int i = 0; i < h; i++)
+			for (int j = 0; j < w; j++)
+				sgp_pixel<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[i * w + j], s);
+	}
+	template <int NP>
+	SGP_HD_MEMBER double resid(const double *x) const {
+		const SgPsfModel<NP> m = sgp_model<NP>(x);
+		double ff = 0.;
+		for (int i = 0; i < h; i++)
+			for (int j = 0; j < w; j++) {
+				const double r = sgp_resid<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[i * w + j]);
+				ff += r * r;
+			}
+		return ff;
+	}
+	SGP_HD_MEMBER double flux(double B) const {
+		double t = 0.;
+		for (int p = 0; p < h * w; p++)
+			t += (double)box[p] - B;
+		return t;
+	}
+};
+
+/* ---------------------------------------------------------------- peaker: finish and is_star */
 
 /* the fitted fields shared by sg_star and sg_starfit_cand */
 struct SgPsfFit {
@@ -503,7 +613,7 @@ SGP_HD void sgp_fit_clear(SgPsfFit &o, int status) {
 	o.failed_test = 0;
 }
 
-/* the fit after the start values, on any evaluator (which also gives ev.flux(B), the sum of z - B) */
+/* peaker's fit after the start values, on any evaluator */
 template <class Ev>
 SGP_HD void sgp_fit(Ev &ev, const double init[SGP_NP], int n2, int cx, int cy, double norm, double scale_x,
 		double scale_y, double roundness, SgPsfFit &o) {
@@ -514,7 +624,7 @@ SGP_HD void sgp_fit(Ev &ev, const double init[SGP_NP], int n2, int cx, int cy, d
 	double x[SGP_NP], ff;
 	for (int k = 0; k < SGP_NP; k++)
 		x[k] = init[k];
-	const int bad = sgp_lm(ev, x, &ff, &o.iters);
+	const int bad = sgp_lm<SGP_NP>(ev, x, &ff, &o.iters);
 	double t = ff;
 	for (int k = 0; k < SGP_NP; k++)
 		t += x[k];
@@ -525,38 +635,12 @@ SGP_HD void sgp_fit(Ev &ev, const double init[SGP_NP], int n2, int cx, int cy, d
 	sgp_finish(x, ff, ev.flux(x[0]), n, n2 / 2, cx, cy, norm, scale_x, scale_y, roundness, o);
 }
 
-/* the sequential evaluator: every sum in matrix order */
-struct SgPsfSeqEval {
-	const uint16_t *box;
-	int n2;
-	SGP_HD_MEMBER void full(const double x[SGP_NP], SgPsfSums &s) const {
-		sgp_sums_zero(s);
-		for (int i = 0; i < n2; i++)
-			for (int j = 0; j < n2; j++)
-				sgp_pixel(x, (double)(j + 1), (double)(i + 1), (double)box[i * n2 + j], s);
-	}
-	SGP_HD_MEMBER double resid(const double x[SGP_NP]) const {
-		double ff = 0.;
-		for (int i = 0; i < n2; i++)
-			for (int j = 0; j < n2; j++) {
-				const double r = sgp_resid(x, (double)(j + 1), (double)(i + 1), (double)box[i * n2 + j]);
-				ff += r * r;
-			}
-		return ff;
-	}
-	SGP_HD_MEMBER double flux(double B) const {
-		double t = 0.;
-		for (int p = 0; p < n2 * n2; p++)
-			t += (double)box[p] - B;
-		return t;
-	}
-};
-
 /* a whole box sequentially: psf_global_minimisation(z, bg, layer, FALSE, FALSE), psf_update_units,
  * is_star and xpos / ypos of the candidate (cx, cy); box[i * 2r + j], r >= 1 */
 static inline void sg_psf_fit_box(const uint16_t *box, int r, double bg, int cx, int cy, double norm, double scale_x,
 		double scale_y, double roundness, double init[SGP_NP], SgPsfFit &o) {
-	SgPsfSeqEval ev = {box, 2 * r};
-	sgp_init_box(box, 2 * r, bg, init);
-	sgp_fit(ev, init, 2 * r, cx, cy, norm, scale_x, scale_y, roundness, o);
+	const int n2 = 2 * r;
+	SgPsfSeqEval ev = {box, n2, n2};
+	sgp_init_box(box, n2, n2, bg, [n2](const uint16_t *b, int i, int j) { return sgp_median3x3(b, n2, i, j); }, init);
+	sgp_fit(ev, init, n2, cx, cy, norm, scale_x, scale_y, roundness, o);
 }

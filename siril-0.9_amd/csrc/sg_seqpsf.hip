@@ -6,7 +6,7 @@
  *     into LDS as u16 once; the non-zero median is a two-pass radix select over the LDS box (8 + 8
  *     bits, integer and exact); the first maximum of the 3x3-median-filtered box is a 64-bit ordered
  *     key reduction (value above, 2^32 - 1 - index below: 16384 pixels do not fit beside a 16-bit
- *     value in 32 bits); the two fits run sg_seqpsf.h's solver in every thread on a workgroup-wide
+ *     value in 32 bits); the two fits run sg_psf.h's solver in every thread on a workgroup-wide
  *     evaluator: pixels strided over the threads, a butterfly per wave, the waves' partial sums added
  *     in wave order through LDS.  Every thread holds the same bits, so the solver's branches, and the
  *     barriers inside the evaluator, are workgroup-uniform.
@@ -91,30 +91,30 @@ __device__ static inline void sgq_block_sum(double *v, double *part, int tid) {
 	}
 }
 
-/* the evaluator of sq_lm over a box in LDS: pixel q = i * w + j belongs to thread q % T */
+/* the evaluator of sgp_lm over a box in LDS: pixel q = i * w + j belongs to thread q % T */
 template <int T>
 struct SgqEval {
 	const uint16_t *box;
 	double *part;
 	int w, ne, tid;
 	template <int NP>
-	__device__ void full(const double *x, SqSums<NP> &s) const {
-		static_assert(sizeof(SqSums<NP>) == (NP * (NP + 1) / 2 + NP + 1) * sizeof(double), "a plain row of doubles");
-		sq_sums_zero<NP>(s);
-		const SqModel<NP> m = sq_model<NP>(x);
+	__device__ void full(const double *x, SgPsfSums<NP> &s) const {
+		static_assert(sizeof(SgPsfSums<NP>) == (NP * (NP + 1) / 2 + NP + 1) * sizeof(double), "a plain row of doubles");
+		sgp_sums_zero<NP>(s);
+		const SgPsfModel<NP> m = sgp_model<NP>(x);
 		for (int q = tid; q < ne; q += T) {
 			const int i = q / w, j = q - i * w;
-			sq_pixel<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[q], s);
+			sgp_pixel<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[q], s);
 		}
 		sgq_block_sum<T, NP *(NP + 1) / 2 + NP + 1>(&s.a[0], part, tid);
 	}
 	template <int NP>
 	__device__ double resid(const double *x) const {
-		const SqModel<NP> m = sq_model<NP>(x);
+		const SgPsfModel<NP> m = sgp_model<NP>(x);
 		double ff = 0.;
 		for (int q = tid; q < ne; q += T) {
 			const int i = q / w, j = q - i * w;
-			const double r = sq_resid<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[q]);
+			const double r = sgp_resid<NP>(x, m, (double)(j + 1), (double)(i + 1), (double)box[q]);
 			ff += r * r;
 		}
 		sgq_block_sum<T, 1>(&ff, part, tid);
@@ -224,7 +224,7 @@ __device__ static __forceinline__ void sgq_frame(const SgSeqpsfParams &p, int f,
 		__syncthreads();
 	}
 	const int best = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
-	sq_init_walks(L.box, h, w, o.bg, best / w, best % w, (uint16_t)(key >> 32), o.init);
+	sgp_init_walks(L.box, h, w, o.bg, best / w, best % w, (uint16_t)(key >> 32), o.init);
 	SgqEval<T> ev = {L.box, L.part, w, ne, tid};
 	sq_fit(ev, w, h, p.fit_angle, p.norm, p.scale_x, p.scale_y, o);
 }

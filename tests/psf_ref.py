@@ -5,7 +5,8 @@ and of siril-0.9_amd/csrc/sg_psf.h.
   piece                 here
   psf_init_data         init_literal (getMedian3x3 with its zero padding and pointer offset, as written)
   psf_Gaussian_f / _df  model (the reference's formulas, vectorised over the box)
-  lmsder                fit (MINPACK lmder / lmpar in the scaled variables y = D p; see sg_psf.h)
+  lmsder                lm (MINPACK lmder / lmpar in the scaled variables y = D p; see sg_psf.h), for any
+                        parameter count and model: seqpsf_ref runs it with p = 6 and p = 7
   finish, is_star       finish, is_star
   peaker :200-247       peaker_tail
 
@@ -188,15 +189,17 @@ def flux(z, B, v):
         return F64(_total((z.reshape(-1) - F64(B))[:, None], dict(v, fma="off"))[0])
 
 
-# ---------------------------------------------------------------------------- 6 x 6 linear algebra
+# ---------------------------------------------------------------------------- p x p linear algebra
+# (p is read from the arguments: 6 here, 6 and 7 in seqpsf_ref)
 
 def _chol(At, par):
     """L L^T = At + par I as sg_psf.h does it; (L, ri = 1 / diag L, ok)"""
-    L = np.zeros((NP, NP), dtype=F64)
-    ri = np.zeros(NP, dtype=F64)
+    p = At.shape[0]
+    L = np.zeros((p, p), dtype=F64)
+    ri = np.zeros(p, dtype=F64)
     ok = True
     with np.errstate(all="ignore"):
-        for j in range(NP):
+        for j in range(p):
             d = At[j, j] + par
             for k in range(j):
                 d = d - L[j, k] * L[j, k]
@@ -206,7 +209,7 @@ def _chol(At, par):
             rl = 1.0 / l
             L[j, j] = l
             ri[j] = rl
-            for i in range(j + 1, NP):
+            for i in range(j + 1, p):
                 val = At[i, j]
                 for k in range(j):
                     val = val - L[i, k] * L[j, k]
@@ -217,7 +220,7 @@ def _chol(At, par):
 def _fwd(L, ri, w):
     w = w.copy()
     with np.errstate(all="ignore"):
-        for i in range(NP):
+        for i in range(len(w)):
             val = w[i]
             for k in range(i):
                 val = val - L[i, k] * w[k]
@@ -227,21 +230,31 @@ def _fwd(L, ri, w):
 
 def _bwd(L, ri, w):
     w = w.copy()
+    n = len(w)
     with np.errstate(all="ignore"):
-        for i in range(NP - 1, -1, -1):
+        for i in range(n - 1, -1, -1):
             val = w[i]
-            for k in range(i + 1, NP):
+            for k in range(i + 1, n):
                 val = val - L[k, i] * w[k]
             w[i] = val * ri[i]
     return w
 
 
-def _norm6(v):
+def _norm(v):
     t = F64(0.0)
     with np.errstate(all="ignore"):
-        for k in range(NP):
+        for k in range(len(v)):
             t = t + v[k] * v[k]
         return np.sqrt(t)
+
+
+def _solve(L, ri, gt):
+    """(y = (L L^T)^-1 gt, |y|, |L^-1 (y / |y|)|^2)"""
+    y = _bwd(L, ri, _fwd(L, ri, gt))
+    n = _norm(y)
+    with np.errstate(all="ignore"):
+        wn = _norm(_fwd(L, ri, y / n))
+    return y, n, wn * wn
 
 
 class _Chol:
@@ -255,11 +268,7 @@ class _Chol:
         return ok
 
     def solve(self):
-        y = _bwd(self.L, self.ri, _fwd(self.L, self.ri, self.gt))
-        n = _norm6(y)
-        with np.errstate(all="ignore"):
-            wn = _norm6(_fwd(self.L, self.ri, y / n))
-        return y, n, wn * wn
+        return _solve(self.L, self.ri, self.gt)
 
 
 class _QR:
@@ -270,7 +279,7 @@ class _QR:
 
     def factor(self, par):
         with np.errstate(all="ignore"):
-            M = np.concatenate([self.Js, math.sqrt(par) * np.eye(NP)]) if par > 0 else self.Js
+            M = np.concatenate([self.Js, math.sqrt(par) * np.eye(self.Js.shape[1])]) if par > 0 else self.Js
             if not np.isfinite(M).all():
                 return False
             self.R = np.linalg.qr(M, mode="r")
@@ -281,11 +290,7 @@ class _QR:
         L = self.R.T.copy()
         with np.errstate(all="ignore"):
             ri = 1.0 / np.diag(L)
-        y = _bwd(L, ri, _fwd(L, ri, self.gt))
-        n = _norm6(y)
-        with np.errstate(all="ignore"):
-            wn = _norm6(_fwd(L, ri, y / n))
-        return y, n, wn * wn
+        return _solve(L, ri, self.gt)
 
 
 def lmpar(fac, gt, delta, par):
@@ -300,7 +305,7 @@ def lmpar(fac, gt, delta, par):
             par_lower = fp / (delta * phider) if phider > 0.0 else F64(0.0)
         else:
             dxnorm = fp = F64(np.inf)
-        gnorm = _norm6(gt)
+        gnorm = _norm(gt)
         par_upper = gnorm / delta
         if par_upper == 0.0:
             par_upper = DBL_MIN / min(delta, 0.1)
@@ -316,7 +321,7 @@ def lmpar(fac, gt, delta, par):
             if par == 0.0:
                 par = max(0.001 * par_upper, DBL_MIN)
             if not fac.factor(par):
-                return np.full(NP, np.nan), F64(par)
+                return np.full(len(gt), np.nan), F64(par)
             y, dxnorm, phider = fac.solve()
             fp_old = fp
             fp = dxnorm - delta
@@ -339,12 +344,14 @@ def _finite(*vals):
     return all(bool(np.isfinite(v).all()) for v in vals)
 
 
-def lm(z, init, v):
-    """lmsder as sg_psf.h restates it.  Returns dict(x, ff, iters, bad, trace); trace lists every
-    trial step as (outer, inner, accepted)."""
-    rng = np.random.default_rng(ULP_SEED) if v["exp"] == "ulp" else None
+def lm(z, init, v, sums=sums, resid=resid, seed=ULP_SEED):
+    """lmsder as sg_psf.h restates it, for p = len(init) parameters of the model whose sums(x, z, v, rng)
+    and resid(x, z, v, rng) are given (seqpsf_ref passes its own, and its seed of the exp variant).
+    Returns dict(x, ff, iters, bad, trace); trace lists every trial step as (outer, inner, accepted)."""
+    rng = np.random.default_rng(seed) if v["exp"] == "ulp" else None
     Fac = _QR if v["linalg"] == "qr" else _Chol
     x = np.array(init, dtype=F64)
+    n = len(x)
     trace = []
     with np.errstate(all="ignore"):
         a, g, ff, J = sums(x, z, v, rng)
@@ -352,7 +359,7 @@ def lm(z, init, v):
             return dict(x=x, ff=F64(np.nan), iters=0, bad=True, trace=trace)
         diag = np.sqrt(np.diag(a)).copy()
         diag[diag == 0.0] = 1.0
-        xn = _norm6(diag * x)
+        xn = _norm(diag * x)
         delta = F64(100.0) if xn == 0.0 else 100.0 * xn
         par = F64(0.0)
         first = True
@@ -368,7 +375,7 @@ def lm(z, init, v):
             accepted = False
             for inner in range(MAX_INNER):
                 y, par = lmpar(fac, gt, delta, par)
-                pnorm = _norm6(y)
+                pnorm = _norm(y)
                 if not np.isfinite(pnorm):
                     break
                 p = -(y / diag)
@@ -382,9 +389,9 @@ def lm(z, init, v):
                     u = fnorm1 / fnorm
                     actred = 1.0 - u * u
                 q = F64(0.0)
-                for i in range(NP):
+                for i in range(n):
                     r = F64(0.0)
-                    for j in range(NP):
+                    for j in range(n):
                         r = r + At[i, j] * y[j]
                     q = q + y[i] * r
                 t1 = np.sqrt(q if q > 0.0 else F64(0.0)) / fnorm

@@ -11,7 +11,7 @@ oracle of sg_seqpsf_u16* / sg_seqpsf_shifts (include/sirilgpu.h) and of siril-0.
   psf_init_data                        psf_ref.init_literal (it already takes an h x w matrix)
   psf_Gaussian_f / _df                 psf_ref.model
   psf_Gaussian_f_an / _df_an           model_angle (the reference's formulas, as written)
-  lmsder, p = 6 and p = 7              lm (psf_ref.lm with the parameter count left open)
+  lmsder, p = 6 and p = 7              lm (psf_ref.lm on the sums of this module)
   psf_minimiz_angle's and psf_global_minimisation's finish, the hook     fit_box
   register_shift_fwhm :424-489         shifts
 
@@ -36,8 +36,7 @@ import numpy as np
 import psf_ref as pr
 
 F64 = np.float64
-MAX_ITER, MAX_INNER, MAX_LMPAR = 10, 10, 10
-DBL_MIN = 2.2250738585072014e-308
+MAX_ITER = pr.MAX_ITER
 EPSILON = 0.01
 MAX_FOLD = 8
 THREADS = 256                       # SGQ_THREADS of sg_seqpsf_plan.hpp
@@ -190,232 +189,11 @@ def flux(z, B, v):
         return F64(_total((z.reshape(-1) - F64(B))[:, None], dict(v, fma="off"))[0])
 
 
-# ---------------------------------------------------------------------------- p x p linear algebra (psf_ref's)
-
-def _chol(At, par):
-    p = At.shape[0]
-    L = np.zeros((p, p), dtype=F64)
-    ri = np.zeros(p, dtype=F64)
-    ok = True
-    with np.errstate(all="ignore"):
-        for j in range(p):
-            d = At[j, j] + par
-            for k in range(j):
-                d = d - L[j, k] * L[j, k]
-            if not d > 0.0:
-                ok = False
-            l = np.sqrt(d)
-            rl = 1.0 / l
-            L[j, j] = l
-            ri[j] = rl
-            for i in range(j + 1, p):
-                val = At[i, j]
-                for k in range(j):
-                    val = val - L[i, k] * L[j, k]
-                L[i, j] = val * rl
-    return L, ri, ok
-
-
-def _fwd(L, ri, w):
-    w = w.copy()
-    with np.errstate(all="ignore"):
-        for i in range(len(w)):
-            val = w[i]
-            for k in range(i):
-                val = val - L[i, k] * w[k]
-            w[i] = val * ri[i]
-    return w
-
-
-def _bwd(L, ri, w):
-    w = w.copy()
-    n = len(w)
-    with np.errstate(all="ignore"):
-        for i in range(n - 1, -1, -1):
-            val = w[i]
-            for k in range(i + 1, n):
-                val = val - L[k, i] * w[k]
-            w[i] = val * ri[i]
-    return w
-
-
-def _norm(v):
-    t = F64(0.0)
-    with np.errstate(all="ignore"):
-        for k in range(len(v)):
-            t = t + v[k] * v[k]
-        return np.sqrt(t)
-
-
-def _solve(L, ri, gt):
-    y = _bwd(L, ri, _fwd(L, ri, gt))
-    n = _norm(y)
-    with np.errstate(all="ignore"):
-        wn = _norm(_fwd(L, ri, y / n))
-    return y, n, wn * wn
-
-
-class _Chol:
-    def __init__(self, At, gt, Js):
-        self.At, self.gt = At, gt
-
-    def factor(self, par):
-        self.L, self.ri, ok = _chol(self.At, par)
-        return ok
-
-    def solve(self):
-        return _solve(self.L, self.ri, self.gt)
-
-
-class _QR:
-    """Householder QR of [J D^-1; sqrt(par) I]: R^T R = At + par I without forming At"""
-
-    def __init__(self, At, gt, Js):
-        self.Js, self.gt = Js, gt
-
-    def factor(self, par):
-        p = self.Js.shape[1]
-        with np.errstate(all="ignore"):
-            M = np.concatenate([self.Js, math.sqrt(par) * np.eye(p)]) if par > 0 else self.Js
-            if not np.isfinite(M).all():
-                return False
-            self.R = np.linalg.qr(M, mode="r")
-        d = np.abs(np.diag(self.R))
-        return bool((d > 0).all() and np.isfinite(self.R).all())
-
-    def solve(self):
-        L = self.R.T.copy()
-        with np.errstate(all="ignore"):
-            ri = 1.0 / np.diag(L)
-        return _solve(L, ri, self.gt)
-
-
-def lmpar(fac, gt, delta, par):
-    """MINPACK lmpar in the scaled variables: (y = D p, par); psf_ref.lmpar for any p"""
-    par_lower = F64(0.0)
-    with np.errstate(all="ignore"):
-        if fac.factor(0.0):
-            y, dxnorm, phider = fac.solve()
-            fp = dxnorm - delta
-            if fp <= 0.1 * delta:
-                return y, F64(0.0)
-            par_lower = fp / (delta * phider) if phider > 0.0 else F64(0.0)
-        else:
-            dxnorm = fp = F64(np.inf)
-        gnorm = _norm(gt)
-        par_upper = gnorm / delta
-        if par_upper == 0.0:
-            par_upper = DBL_MIN / min(delta, 0.1)
-        if par > par_upper:
-            par = par_upper
-        elif par < par_lower:
-            par = par_lower
-        if par == 0.0:
-            par = gnorm / dxnorm
-        it = 0
-        while True:
-            it += 1
-            if par == 0.0:
-                par = max(0.001 * par_upper, DBL_MIN)
-            if not fac.factor(par):
-                return np.full(len(gt), np.nan), F64(par)
-            y, dxnorm, phider = fac.solve()
-            fp_old = fp
-            fp = dxnorm - delta
-            if abs(fp) <= 0.1 * delta or (par_lower == 0.0 and fp <= fp_old and fp_old < 0.0) or it == MAX_LMPAR:
-                break
-            par_c = fp / (delta * phider)
-            if fp > 0.0:
-                if par > par_lower:
-                    par_lower = par
-            elif fp < 0.0:
-                if par < par_upper:
-                    par_upper = par
-            par = par + par_c if par + par_c > par_lower else par_lower
-    return y, F64(par)
-
+# ---------------------------------------------------------------------------- the fit
 
 def lm(z, init, v):
-    """lmsder as sg_seqpsf.h restates it, p = len(init).  dict(x, ff, iters, bad, trace)"""
-    rng = np.random.default_rng(ULP_SEED) if v["exp"] == "ulp" else None
-    Fac = _QR if v["linalg"] == "qr" else _Chol
-    x = np.array(init, dtype=F64)
-    p = len(x)
-    trace = []
-    with np.errstate(all="ignore"):
-        a, g, ff, J = sums(x, z, v, rng)
-        if not pr._finite(a, g, ff):
-            return dict(x=x, ff=F64(np.nan), iters=0, bad=True, trace=trace)
-        diag = np.sqrt(np.diag(a)).copy()
-        diag[diag == 0.0] = 1.0
-        xn = _norm(diag * x)
-        delta = F64(100.0) if xn == 0.0 else 100.0 * xn
-        par = F64(0.0)
-        first = True
-        iters = 0
-        for outer in range(1, MAX_ITER + 1):
-            iters = outer
-            fnorm = np.sqrt(ff)
-            if fnorm == 0.0:
-                break
-            gt = g / diag
-            At = a / np.outer(diag, diag)
-            fac = Fac(At, gt, J / diag[None, :])
-            accepted = False
-            for inner in range(MAX_INNER):
-                y, par = lmpar(fac, gt, delta, par)
-                pnorm = _norm(y)
-                if not np.isfinite(pnorm):
-                    break
-                step = -(y / diag)
-                xt = x + step
-                if first and pnorm < delta:
-                    delta = pnorm
-                ff1 = resid(xt, z, v, rng)
-                fnorm1 = np.sqrt(ff1)
-                actred = F64(-1.0)
-                if 0.1 * fnorm1 < fnorm:
-                    u = fnorm1 / fnorm
-                    actred = 1.0 - u * u
-                q = F64(0.0)
-                for i in range(p):
-                    r = F64(0.0)
-                    for j in range(p):
-                        r = r + At[i, j] * y[j]
-                    q = q + y[i] * r
-                t1 = np.sqrt(q if q > 0.0 else F64(0.0)) / fnorm
-                t2 = np.sqrt(par) * pnorm / fnorm
-                prered = t1 * t1 + t2 * t2 / 0.5
-                dirder = -(t1 * t1 + t2 * t2)
-                ratio = actred / prered if prered > 0.0 else F64(0.0)
-                if ratio > 0.25:
-                    if par == 0.0 or ratio >= 0.75:
-                        delta = pnorm / 0.5
-                        par = par * 0.5
-                else:
-                    temp = F64(0.5) if actred >= 0.0 else 0.5 * dirder / (dirder + 0.5 * actred)
-                    if 0.1 * fnorm1 >= fnorm or temp < 0.1:
-                        temp = F64(0.1)
-                    delta = temp * min(delta, pnorm / 0.1)
-                    par = par / temp
-                ok = bool(ratio >= 1e-4)
-                trace.append((outer, inner, ok))
-                if ok:
-                    x = xt
-                    a, g, ff, J = sums(x, z, v, rng)
-                    if not pr._finite(a, g, ff):
-                        return dict(x=x, ff=ff, iters=iters, bad=True, trace=trace)
-                    first = False
-                    diag = np.maximum(diag, np.sqrt(np.diag(a)))
-                    accepted = True
-                    break
-            if not accepted:
-                trace.append((outer, "no progress"))
-                break
-            if bool((np.abs(step) < 1e-4 + 1e-4 * np.abs(x)).all()):
-                trace.append((outer, "delta test"))
-                break
-    return dict(x=x, ff=ff, iters=iters, bad=False, trace=trace)
+    """psf_ref.lm on this module's sums (either model, the device's order of addition), p = len(init)"""
+    return pr.lm(z, init, v, sums, resid, ULP_SEED)
 
 
 # ---------------------------------------------------------------------------- a frame
