@@ -445,8 +445,8 @@ int sg_prepro_noise_device(sg_ctx *ctx, int dev_index, sg_prepro *pp, const uint
  * not finite, max_candidates < 0.  2 * radius >= a side of the area is no error: no candidate.
  * Left to the caller: the PSF fit (psf_global_minimisation(z, bg = median, layer, FALSE, FALSE),
  * GSL, unpinned) with xpos = x + x0 - r - 1, ypos = y + y0 - r - 1 (:221-222), is_star, the
- * MAX_STARS cap on accepted stars (the reference has no cap on candidates), sort_stars and the
- * matching (new_star_match); see INTEGRATION.md.
+ * MAX_STARS cap on accepted stars (the reference has no cap on candidates) and sort_stars, which
+ * sg_findstar_fit* does; the matching (new_star_match) is sg_starmatch, below; see INTEGRATION.md.
  */
 typedef struct {
 	int width, height, nb_layers;
@@ -499,8 +499,8 @@ int sg_findstar(sg_ctx *ctx, const sg_findstar_desc *desc, const uint16_t *frame
  * Refused before any device work, beyond what sg_findstar refuses: SG_ERR_GENERIC for radius > 32,
  * roundness or a scale not finite, norm not 255 or 65535, max_stars outside [0, 50000].
  * radius = 1 is no error: every candidate gets SG_FIT_NOT_ENOUGH_PIXELS.
- * Left to the caller: the matching (new_star_match), FWHM_average, the angle fit, the
- * uncertainties, 8-bit frames.
+ * The matching (new_star_match) and FWHM_average take these lists as they are: sg_starmatch, below.
+ * Left to the caller: the angle fit, the uncertainties, 8-bit frames.
  */
 #define SG_STARFIT_MAX_RADIUS 32
 #define SG_STARFIT_MAX_STARS 50000	/* MAX_STARS */
@@ -829,6 +829,58 @@ int sg_seqpsf_last_times(sg_ctx *ctx, int dev_index, double *ms, int *launches);
  * 0, scanning in frame order without revisiting the reference.  fwhm, best_index, best_fwhm may be NULL. */
 int sg_seqpsf_shifts(int nframes, int ref_image, const sg_seqpsf_frame *per_frame, int *shiftx, int *shifty, double *fwhm,
 		int *best_index, double *best_fwhm);
+
+/*
+ * Star matching of a whole sequence: the middle of register_star_alignment's loop
+ * (src/registration/registration.c:589-755), new_star_match (src/registration/matching/match.c:125-389)
+ * for every frame against the reference frame's list, one workgroup per frame in one launch.  With it
+ * the chain is sg_findstar_fit* -> sg_starmatch -> sg_starmatch_warp_plan -> sg_warp_frames_u16*.
+ * nstars [nframes] and stars [nframes][max_stars] are what sg_findstar_fit* returns (host arrays, each
+ * list ascending by mag); the call packs (xpos, ypos, mag) and uploads it.  fitted_stars = min(nstars[ref],
+ * 2000); frame f is matched with nbpoints = min(nstars[f], fitted_stars) stars of both lists.
+ * Per frame, as the reference: atFindTrans (linear order, 20 brightest, triangle radius 0.002, scale
+ * limits 0.9 .. 1.1, and once more without the scale test if that fails: scale_retry), atApplyTrans,
+ * atMatchLists (radius 5), atCalcRMS (sx, sy), atRecalcTrans over the matched pairs, and cvCalculH:
+ * findHomography with RANSAC (threshold 3, confidence 0.995, at most 2000 iterations, OpenCV's
+ * generator seeded afresh), runKernel on the inliers and refine (at most 10 iterations).
+ * siril-0.9_amd/csrc/sg_starmatch.h is the restatement, tests/starmatch_ref.py its literal numpy form
+ * and the place of the contracts: ties of the reference's qsorts go to the smaller index; the matched
+ * pairs are per A star the nearest candidate (ties to the smaller (x, id) of B), then per B star the
+ * nearest A (ties to the smaller A id), in ascending B id; fewer than 6 winners of 2 votes is a failure
+ * (the reference reads past them).  PARITY-UNPINNED: cvEigenVV and cvSVD are OpenCV internals, restated
+ * as one cyclic Jacobi eigen-solver, as for the warp and ECC.
+ * results [nframes]; status: SG_MATCH_REFERENCE (nbpoints = fitted_stars, hom = identity), EXCLUDED,
+ * FEW_STARS (nstars[f] < 10), NO_TRANS (atFindTrans failed twice), NO_RECALC, NO_HOMOGRAPHY, or OK with
+ * hom = h00 .. h22 as sg_warp_frames_u16* takes it.  nwinners = trans->nr of atFindTrans, trans0 its
+ * TRANS (a .. f), trans / nr_recalc / sig those of atRecalcTrans; fwhmx / fwhmy = FWHM_average over the
+ * first nbpoints stars (OK and REFERENCE frames); shiftx = +h02, shifty = -h12 (translation_only).
+ * pairs: NULL or host [nframes][2000][2] int32 = (A index, B index) of the matched pairs, -1 padded.
+ * The call fails with SG_ERR_GENERIC, writing nothing, when the reference has fewer than 10 stars.
+ * Refused before any device work, with a message: SG_ERR_SIZE for nframes < 1, max_stars < 1 or above
+ * SG_STARFIT_MAX_STARS; SG_ERR_GENERIC for a missing pointer, ref_image out of range, nstars[f] outside
+ * [0, max_stars], a non-finite xpos / ypos / mag among the stars used, an excluded reference.
+ * Synchronous.  sg_starmatch_last_times: the last call's device span and launches.
+ * sg_starmatch_warp_plan (host only) turns the results into the arguments of sg_warp_frames_u16*, with
+ * the loop's failed / skipped bookkeeping: the reference COPY, OK frames APPLY with their hom, every
+ * other frame SKIP; out_slot = frame - failed - skipped; *new_total = the frames written.  hom
+ * [nframes][9], action, out_slot [nframes]; new_total may be NULL.  Returns 0, or -1 for a missing pointer.
+ */
+enum { SG_MATCH_OK = 0, SG_MATCH_REFERENCE = 1, SG_MATCH_EXCLUDED = 2, SG_MATCH_FEW_STARS = 3,
+       SG_MATCH_NO_TRANS = 4, SG_MATCH_NO_RECALC = 5, SG_MATCH_NO_HOMOGRAPHY = 6 };
+#define SG_STARMATCH_MAX_PAIRS 2000	/* MAX_STARS_FITTED */
+
+typedef struct {
+	int32_t status, nbpoints, nbright, scale_retry, nwinners, npairs, nr_recalc, inliers, ransac_iters, lm_iters;
+	double trans0[6], trans[6], sig, sx, sy, hom[9];
+	float fwhmx, fwhmy;
+	double shiftx, shifty;
+} sg_starmatch_result;
+
+int sg_starmatch(sg_ctx *ctx, int dev_index, int nframes, int max_stars, const int32_t *nstars, const sg_star *stars,
+		int ref_image, const uint8_t *included, sg_starmatch_result *results, int32_t *pairs, void *stream);
+int sg_starmatch_last_times(sg_ctx *ctx, int dev_index, double *ms, int *launches);
+int sg_starmatch_warp_plan(const sg_starmatch_result *results, int nframes, double *hom, int *action, int *out_slot,
+		int *new_total);
 
 /* Synthetic sequence generator of include/sg_synth.h on the device (bench / tests):
  * frame f, channel c, row r at d_frames[f*frame_stride + (c*height + r)*width]

@@ -123,7 +123,7 @@ extern "C" void sg_shutdown(sg_ctx *ctx) {
 			(void)hipStreamSynchronize(d.tail);
 		SgBuf *bufs[] = {&d.sum_buf, &d.frames, &d.out, &d.reg_sel, &d.reg_spec, &d.reg_work, &d.reg_tw, &d.reg_tw32,
 			&d.reg_best, &d.reg_qbuf, &d.reg_qacc, &d.zeros, &d.io_raw, &d.io_bad, &d.warp_tab, &d.stats_buf, &d.ctr, &d.fs_work, &d.fs_plane, &d.fs_out,
-			&d.fs_fit, &d.ecc_work, &d.cosme_work, &d.quality_work, &d.host_frames, &d.warp_work, &d.seqpsf_work};
+			&d.fs_fit, &d.ecc_work, &d.cosme_work, &d.quality_work, &d.host_frames, &d.warp_work, &d.seqpsf_work, &d.starmatch_work};
 		for (SgBuf *b : bufs)
 			if (b->p)
 				(void)hipFree(b->p);

@@ -139,6 +139,11 @@ struct SgDevice {
 	SgBuf seqpsf_work;
 	double seqpsf_ms = 0.;
 	int seqpsf_launches = 0;
+	/* star matching (sg_starmatch.hip): the packed lists, the table, the results and the pairs; the
+	 * last call's device span and launches */
+	SgBuf starmatch_work;
+	double starmatch_ms = 0.;
+	int starmatch_launches = 0;
 	hipEvent_t io_ev[2] = {nullptr, nullptr};
 	int io_ev_used[2] = {0, 0};
 };

@@ -169,6 +169,16 @@ SEQPSF_DTYPE = np.dtype([("status", "<i4"), ("angle_fitted", "<i4"), ("iters", "
                          ("noangle", "<f8", (6,))] + [(k, "<f8") for k in SEQPSF_FIELDS])
 assert SEQPSF_DTYPE.itemsize == 240
 
+# sg_starmatch: statuses, sg_starmatch_result as a numpy structured type, the pairs' capacity per frame
+MATCH_OK, MATCH_REFERENCE, MATCH_EXCLUDED, MATCH_FEW_STARS, MATCH_NO_TRANS, MATCH_NO_RECALC, MATCH_NO_HOMOGRAPHY = range(7)
+STARMATCH_INT_FIELDS = ("status", "nbpoints", "nbright", "scale_retry", "nwinners", "npairs", "nr_recalc", "inliers",
+                        "ransac_iters", "lm_iters")
+STARMATCH_DTYPE = np.dtype([(k, "<i4") for k in STARMATCH_INT_FIELDS] +
+                           [("trans0", "<f8", (6,)), ("trans", "<f8", (6,)), ("sig", "<f8"), ("sx", "<f8"), ("sy", "<f8"),
+                            ("hom", "<f8", (9,)), ("fwhmx", "<f4"), ("fwhmy", "<f4"), ("shiftx", "<f8"), ("shifty", "<f8")])
+assert STARMATCH_DTYPE.itemsize == 256
+STARMATCH_MAX_PAIRS = 2000
+
 
 # every symbol include/sirilgpu.h and include/sirilgpu_io.h declare
 EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_u16_device",
@@ -186,7 +196,8 @@ EXPORTS = ["sg_init", "sg_shutdown", "sg_last_error", "sg_stack_u16", "sg_stack_
            "sg_register_ecc_last_times", "sg_cosme_autodetect_device", "sg_cosme_autodetect", "sg_cosme_last_times",
            "sg_quality_u16_device", "sg_quality_u16", "sg_quality_last_times", "sg_quality_normalize", "sg_quality_select",
            "sg_warp_frames_u16_device", "sg_warp_frames_u16", "sg_warp_frames_last_times",
-           "sg_seqpsf_u16_device", "sg_seqpsf_u16", "sg_seqpsf_last_times", "sg_seqpsf_shifts"]
+           "sg_seqpsf_u16_device", "sg_seqpsf_u16", "sg_seqpsf_last_times", "sg_seqpsf_shifts",
+           "sg_starmatch", "sg_starmatch_last_times", "sg_starmatch_warp_plan"]
 # opencv_interpolation (src/core/siril.h:257-264)
 OPENCV_NEAREST, OPENCV_LINEAR, OPENCV_AREA, OPENCV_CUBIC, OPENCV_LANCZOS4 = range(5)
 
@@ -365,6 +376,12 @@ def load():
     lib.sg_seqpsf_shifts.argtypes = [ctypes.c_int, ctypes.c_int, P, P, P, P, ctypes.POINTER(ctypes.c_int),
                                      ctypes.POINTER(ctypes.c_double)]
     lib.sg_seqpsf_shifts.restype = ctypes.c_int
+    lib.sg_starmatch.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, ctypes.c_int, P, P, P, P]
+    lib.sg_starmatch.restype = ctypes.c_int
+    lib.sg_starmatch_last_times.argtypes = [P, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
+    lib.sg_starmatch_last_times.restype = ctypes.c_int
+    lib.sg_starmatch_warp_plan.argtypes = [P, ctypes.c_int, P, P, P, ctypes.POINTER(ctypes.c_int)]
+    lib.sg_starmatch_warp_plan.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -975,6 +992,35 @@ class Context:
         self.check(self.lib.sg_seqpsf_last_times(self.ctx, dev_index, ctypes.byref(a), ctypes.byref(n)), "sg_seqpsf_last_times")
         return a.value, n.value
 
+    def starmatch(self, nstars, stars, ref_image=0, included=None, want_pairs=False, stream=None, dev_index=0):
+        """new_star_match of every frame's star list against the reference frame's (sg_starmatch): nstars [N] and
+        stars [N][max_stars] of STAR_DTYPE as findstar_fit returns them.  Returns (results as a STARMATCH_DTYPE
+        array, pairs [N][2000][2] int32 of (A index, B index), -1 padded, or None).  Raises on a refusal and when
+        the reference frame has fewer than 10 stars; the message is the library's."""
+        nstars = np.ascontiguousarray(nstars, dtype=np.int32)
+        stars = np.ascontiguousarray(stars, dtype=STAR_DTYPE)
+        n = len(nstars)
+        max_stars = stars.shape[1] if stars.ndim == 2 else 0
+        if stars.ndim != 2 or stars.shape[0] != n:
+            raise ValueError("stars must be [len(nstars)][max_stars]")
+        inc = None if included is None else np.ascontiguousarray(included, dtype=np.uint8)
+        if inc is not None and len(inc) != n:
+            raise ValueError("included must have one entry per frame")
+        res = np.zeros(max(n, 1), dtype=STARMATCH_DTYPE)
+        pairs = np.full((max(n, 1), STARMATCH_MAX_PAIRS, 2), -1, dtype=np.int32) if want_pairs else None
+        P = ctypes.c_void_p
+        rc = self.lib.sg_starmatch(self.ctx, dev_index, n, max_stars, nstars.ctypes.data_as(P), stars.ctypes.data_as(P), ref_image,
+                                   inc.ctypes.data_as(P) if inc is not None else None, res.ctypes.data_as(P),
+                                   pairs.ctypes.data_as(P) if pairs is not None else None, P(stream) if stream else None)
+        self.check(rc, "sg_starmatch")
+        return res[:n], (pairs[:n] if pairs is not None else None)
+
+    def starmatch_last_times(self, dev_index=0):
+        """(device ms, kernel launches) of the last starmatch call on that device"""
+        a, n = ctypes.c_double(), ctypes.c_int()
+        self.check(self.lib.sg_starmatch_last_times(self.ctx, dev_index, ctypes.byref(a), ctypes.byref(n)), "sg_starmatch_last_times")
+        return a.value, n.value
+
     def cosme_autodetect_device(self, d_frames, nframes, C, H, W, sig=(3.0, 3.0), amount=1.0, is_cfa=False,
                                 frame_stride=0, stream=None, dev_index=0):
         """seqfind_cosme's per-frame work (autoDetect on every layer) on resident frames, in place
@@ -1199,6 +1245,21 @@ def seqpsf_shifts(records, ref_image=0):
     if rc != 0:
         return rc, None, None, None, None, None
     return rc, sx, sy, fw, bi.value, bf.value
+
+
+def starmatch_warp_plan(results):
+    """the arguments of warp_frames from starmatch's results (sg_starmatch_warp_plan, host only), with the loop's
+    failed / skipped bookkeeping: (hom [N][9], action [N], out_slot [N], new_total)"""
+    rec = np.ascontiguousarray(results, dtype=STARMATCH_DTYPE)
+    n = len(rec)
+    hom, action, slot = np.zeros((n, 9), dtype=np.float64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    total = ctypes.c_int(0)
+    P = ctypes.c_void_p
+    rc = load().sg_starmatch_warp_plan(rec.ctypes.data_as(P), n, hom.ctypes.data_as(P), action.ctypes.data_as(P),
+                                       slot.ctypes.data_as(P), ctypes.byref(total))
+    if rc != 0:
+        raise RuntimeError("sg_starmatch_warp_plan refused its arguments")
+    return hom, action, slot, total.value
 
 
 def compute_normalization(mode, location, scale, ref_image=0):
